@@ -1,6 +1,12 @@
 """bench.py -- throughput of the restoration hot path on MI355X (contract in the round prompt).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the benchmark measures or checks: the roofline figures of the conv family (an extra serial step
+with per-launch events, or per-launch events in the timed region under --no-overlap), the finiteness check of the output,
+configs[2] and the one-GPU share of configs[3] as `extra_configs`, and the CPU baseline.
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (dump_outputs).
 
 N > 1 without a torchrun environment: bench.py starts `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
 CHILD process before anything in this process touches the GPU and exits with its code (rank 0's JSON line passes through);
@@ -49,6 +55,31 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+DUMP_BYTES = 60 << 20   # under 64 MB however a megabyte is counted
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` as path/<name>.npy, float64 kept, everything else as float32, at most DUMP_BYTES in
+    all.  The smaller arrays are written whole; one that does not fit its share of what is left is written as a fixed sample of its
+    flattened elements (seeded: the same indices for the same shape), so that two builds run with the same arguments compare
+    element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES - 4096 * len(items)   # (.npy headers)
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        cap = left // (len(items) - i) // (8 if dtype == torch.float64 else 4)
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            print(f"bench.py: {name}: {cap} of {t.numel()} elements (seeded sample)", file=sys.stderr)
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(dtype).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 PRESETS = {  # BASELINE.json configs[1..3]
     "c2": dict(batch=8, timesteps=50, sampler="ddpm", conv_dtype="f32"),
     "c3": dict(batch=16, timesteps=50, sampler="ddim", ddim_steps=25, conv_dtype="bf16", act_bf16=True),
@@ -86,20 +117,21 @@ def train_bench(args, world, rank, dev):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
-    it = [0]
+    it, losses = [0], [None]
 
     def run(n):
         for _ in range(n):
             it[0] += 1
-            tr.step(it[0], low, real)                           # iterations 1 .. : the R1 pass falls on every 16th
+            losses[0] = tr.step(it[0], low, real)               # iterations 1 .. : the R1 pass falls on every 16th
     run(args.warmup)
-    prof = hip_ops.ConvProfiler()
-    hip_ops.PROFILER = prof
-    run(1)
-    hip_ops.PROFILER = None
-    sync()
-    fl, conv_ms, n_launch = prof.summary()
-    ex_fl = prof.executed_flops()      # what the matrix pipe ran: Winograd launches at 16/36 (F(2x2)) or 36/144 (F(4x4)) of their algorithmic count
+    if args.full:
+        prof = hip_ops.ConvProfiler()
+        hip_ops.PROFILER = prof
+        run(1)
+        hip_ops.PROFILER = None
+        sync()
+        fl, conv_ms, n_launch = prof.summary()
+        ex_fl = prof.executed_flops()  # what the matrix pipe ran: Winograd launches at 16/36 (F(2x2)) or 36/144 (F(4x4)) of their algorithmic count
     # The R1 pass (a double backward through D) runs on every d_reg_every-th iteration: the timed region starts right after a
     # multiple of it, so that K timed iterations contain exactly floor(K / d_reg_every) of them -- one in sixteen with the default
     # K = 16 of this preset, as in the schedule being priced; the count is stated in the line.
@@ -116,8 +148,10 @@ def train_bench(args, world, rank, dev):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
     dt = float(dt)
     if rank == 0:
+        if args.dump_outputs:   # the loss dict of the last timed iteration (this rank's losses)
+            dump_outputs(args.dump_outputs, {k: v for k, v in losses[0].items() if torch.is_tensor(v)})
         ms = dt / args.steps * 1e3
-        print(json.dumps({
+        line = {
             "metric": "restoration_train.py images/sec (512x512, RestoreNet + Discriminator fwd/bwd + LPIPS + id_loss + Adam + EMA)",
             "value": round(world * B / ms * 1e3, 3), "unit": "img/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms, 2), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -126,16 +160,19 @@ def train_bench(args, world, rank, dev):
                                    "Code_diffuser(T=4) + StyleGAN2 prior front, random-init weights, RCCL gradient all-reduce "
                                    "from inside backward (64 MB buckets)" % B, "global_batch": world * B},
             "r1": {"d_reg_every": tr.d_reg_every, "r1_iterations_in_timed_region": n_r1,
-                   "note": "the timed region starts right after a multiple of d_reg_every; K a multiple of it prices the schedule exactly"},
-            "roofline": {"bound": "mfma", "achieved": round(ex_fl / conv_ms / 1e9, 1), "peak": 157.3, "unit": "TFLOP/s",
-                         "frac": round(ex_fl / conv_ms / 1e9 / 157.3, 3), "traffic": None,
-                         "algorithmic_tflops": round(fl / conv_ms / 1e9, 1), "algorithmic_frac": round(fl / conv_ms / 1e9 / 157.3, 3),
-                         "kernel": "conv family of one iteration (forward, data gradient, weight gradient, loss networks); achieved / frac = FLOPs "
-                                   "the matrix pipe EXECUTED / kernel time (Winograd launches run 16/36 or 36/144 of their direct-form count); "
-                                   "algorithmic_* = direct-form FLOPs / time (an effective rate)",
-                         "launches": n_launch, "kernel_ms": round(conv_ms, 1),
-                         "measured": "HIP events per launch on the launch stream over one untimed iteration"},
-            "cpu_baseline": None}))
+                   "note": "the timed region starts right after a multiple of d_reg_every; K a multiple of it prices the schedule exactly"}}
+        if args.full:
+            line["roofline"] = {
+                "bound": "mfma", "achieved": round(ex_fl / conv_ms / 1e9, 1), "peak": 157.3, "unit": "TFLOP/s",
+                "frac": round(ex_fl / conv_ms / 1e9 / 157.3, 3), "traffic": None,
+                "algorithmic_tflops": round(fl / conv_ms / 1e9, 1), "algorithmic_frac": round(fl / conv_ms / 1e9 / 157.3, 3),
+                "kernel": "conv family of one iteration (forward, data gradient, weight gradient, loss networks); achieved / frac = FLOPs "
+                          "the matrix pipe EXECUTED / kernel time (Winograd launches run 16/36 or 36/144 of their direct-form count); "
+                          "algorithmic_* = direct-form FLOPs / time (an effective rate)",
+                "launches": n_launch, "kernel_ms": round(conv_ms, 1),
+                "measured": "HIP events per launch on the launch stream over one untimed iteration"}
+        line["cpu_baseline"] = None
+        print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
     return 0
@@ -293,6 +330,7 @@ def measure(args, world, rank, dev, pipe=None):
     step_no = [0]
     from vspbfr_amd.pipeline import RestoredGather
     gatherer = RestoredGather()   # preallocated, asynchronous: the exchange of batch i runs under C + D of batch i+1
+    last = [None]                 # the dict the pipeline returned for the latest batch (this rank's; --dump-outputs)
 
     def batches(n):
         """n steps: the same LQ shard with fresh noise -- step k restores global images [k*W*B, (k+1)*W*B)."""
@@ -320,12 +358,15 @@ def measure(args, world, rank, dev, pipe=None):
             pending = h
         if args.no_overlap:
             for x, i0 in batches(n):
-                exchange(pipe(x, image_index0=i0)["restored"])
+                last[0] = pipe(x, image_index0=i0)
+                exchange(last[0]["restored"])
         elif args.graphs:
             for o in pipe.run_batches_graphed(batches(n)):
+                last[0] = o
                 exchange(o["restored"], reused=True)
         else:
             for o in pipe.run_batches(batches(n)):
+                last[0] = o
                 exchange(o["restored"])
         if pending is not None:
             res = pending.result()
@@ -341,7 +382,7 @@ def measure(args, world, rank, dev, pipe=None):
             pipe.capture_graphs(lq)
         run(args.warmup)
         iso = None
-        if not args.no_overlap:
+        if args.full and not args.no_overlap:
             # one extra UNTIMED serial step with per-launch events: the conv kernels' durations with nothing else on the GPU
             # (in the timed, overlapped region a conv's event interval also contains the side stream's kernels)
             pipe(lq)  # the serial call path allocates from the main stream's pool: warm it before measuring
@@ -353,7 +394,7 @@ def measure(args, world, rank, dev, pipe=None):
             torch.cuda.synchronize()
         # Per-launch events inside the timed region only for the serial loop (--no-overlap), where they ARE the kernel durations; the
         # default overlapped loop takes every roofline figure from the `iso` step above and times K clean steps.
-        prof = hip_ops.ConvProfiler() if iso is None else None
+        prof = hip_ops.ConvProfiler() if args.full and iso is None else None
         hip_ops.PROFILER = prof
         sync()
         t0 = time.perf_counter()
@@ -361,15 +402,18 @@ def measure(args, world, rank, dev, pipe=None):
         sync()
         dt = time.perf_counter() - t0
         hip_ops.PROFILER = None
-    assert torch.isfinite(res).all(), "non-finite output"
+    if args.full:
+        assert torch.isfinite(res).all(), "non-finite output"
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:   # N > 1: `restored` is the gathered global batch, the other arrays rank 0's shard
+        dump_outputs(args.dump_outputs, {k: v for k, v in dict(last[0], restored=res).items() if torch.is_tensor(v)})   # (--no-sample: no style_sample)
     if prof is not None:
         conv_flops, conv_ms, conv_launches = prof.summary()
         conv_exec = prof.executed_flops()
-    else:   # the serial measurement step, scaled to the K timed steps (the line's per-step fields divide by K again)
+    elif iso is not None:   # the serial measurement step, scaled to the K timed steps (the line's per-step fields divide by K again)
         conv_flops, conv_ms, conv_launches = (v * args.steps for v in iso.summary())
         conv_exec = iso.executed_flops() * args.steps
 
@@ -378,7 +422,6 @@ def measure(args, world, rank, dev, pipe=None):
     line = None
     if rank == 0:
         imgs = world * B * args.steps
-        achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
         # bf16 configuration: the dense bf16 MFMA peak (MI355X_MICROARCH.md); the conv family then mixes bf16 (stride-1 3x3)
         # and fp32 (stride-2, transposed, small-map) launches, all priced against the bf16 peak
         PEAK = {"f32": PEAK_FP32_TFLOPS, "bf16": 2500.0, "bf16x3": 2500.0 / 3}[args.conv_dtype]  # bf16x3: three MFMAs per product
@@ -408,18 +451,21 @@ def measure(args, world, rank, dev, pipe=None):
                        "rng": "torch device RNG, one randn per consumer" if args.torch_rng else
                               "keyed Philox draws by (seed, global image index): 2 launches per batch; the DRAWS are world-size invariant (mixing = 0: no per-batch style-mixing coin), the kernels' summation orders follow the per-rank batch size",
                        "sharding": f"dp{world}: batch split, weights replicated, all-gather of restored images" if world > 1 else "single GPU"},
+        }
+        if args.full:
+            achieved = conv_flops / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
             # achieved / frac = what the matrix pipe EXECUTED per second (<= peak by construction: a Winograd F(2x2,3x3) launch runs 16/36, an
             # F(4x4,3x3) launch 36/144 of its direct-form count); algorithmic_* = direct-form FLOPs / time, an effective rate that may exceed 1
-            "roofline": {"bound": "mfma", "achieved": round(conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0, 2), "peak": PEAK, "unit": "TFLOP/s",
-                         "frac": round((conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0) / PEAK, 4),
-                         "algorithmic_tflops": round(achieved, 2), "algorithmic_frac": round(achieved / PEAK, 4),
-                         "traffic": conv_traffic(B, args),
-                         "kernel": KERNEL_NOTE, "launches_per_step": conv_launches // max(args.steps, 1),
-                         "algorithmic_gflop_per_step": round(conv_flops / max(args.steps, 1) / 1e9, 1),
-                         "kernel_ms_per_step": round(conv_ms / max(args.steps, 1), 2),
-                         "pipeline_frac_of_fp32_peak": round(imgs / dt * ALGO_GFLOP_PER_IMAGE(args.timesteps) / 1e3 / (PEAK * world), 4)},
-        }
-        if args.conv_dtype == "bf16":
+            line["roofline"] = {
+                "bound": "mfma", "achieved": round(conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0, 2), "peak": PEAK, "unit": "TFLOP/s",
+                "frac": round((conv_exec / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0) / PEAK, 4),
+                "algorithmic_tflops": round(achieved, 2), "algorithmic_frac": round(achieved / PEAK, 4),
+                "traffic": conv_traffic(B, args),
+                "kernel": KERNEL_NOTE, "launches_per_step": conv_launches // max(args.steps, 1),
+                "algorithmic_gflop_per_step": round(conv_flops / max(args.steps, 1) / 1e9, 1),
+                "kernel_ms_per_step": round(conv_ms / max(args.steps, 1), 2),
+                "pipeline_frac_of_fp32_peak": round(imgs / dt * ALGO_GFLOP_PER_IMAGE(args.timesteps) / 1e3 / (PEAK * world), 4)}
+        if args.full and args.conv_dtype == "bf16":
             # BASELINE configs[2] / SURVEY 8d: with the bf16 matrix pipe (2.5 PFLOP/s) the conv family is bound by HBM, not by MFMA.
             # achieved = ALGORITHMIC bytes (every operand of a launch crosses HBM once at its element size: input, output, weights,
             # noise, residuals) / kernel time, against the 8 TB/s HBM3E peak; the MFMA figure stays in the line as `mfma`.
@@ -465,6 +511,7 @@ def extra_configs(args, world, rank, dev, pipe):
         for k, v in PRESETS[name].items():
             setattr(a, k, v)
         a.preset = name
+        a.dump_outputs = None   # (the headline configuration's outputs only)
         try:
             ln, _ = measure(a, world, rank, dev, pipe)
             out[key] = {k: ln[k] for k in ("value", "unit", "ms_per_step", "steps", "warmup", "dtype", "config", "roofline")}
@@ -484,7 +531,7 @@ def main():
     ap.add_argument("--no-sample", action="store_true", help="skip the 1024^2 tail of the prior (not the headline config)")
     ap.add_argument("--sampler", choices=["ddpm", "ddim"], default="ddpm", help="ddim = BASELINE configs[2]'s sampler (fp32 here)")
     ap.add_argument("--ddim-steps", type=int, default=25)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-overlap", action="store_true", help="plain per-batch loop (no A+B / C+D stream overlap across batches)")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--graphs", action="store_true",
@@ -505,11 +552,18 @@ def main():
     ap.add_argument("--encoder", choices=["same", "f32", "x3"], default="same",
                     help="bf16 configurations: the kernels of stage A (e4e encoder) -- same as stages C + D (default), fp32, or the split-precision "
                          "bf16 kernels (fp32-grade codes for the sampler chain, which amplifies the encoder's rounding)")
-    ap.add_argument("--no-extra", action="store_true", help="headline configuration only: skip the extra_configs legs (configs[2], the one-GPU "
-                                                             "share of configs[3]) that a default one-GPU run appends to its JSON line")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra_configs legs (configs[2], the one-GPU share of "
+                                                             "configs[3]) that a default one-GPU --full run appends to its JSON line")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline figure: roofline figures of the conv family, "
+                                                         "finiteness check, extra_configs, CPU baseline (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, "
+                         "under 64 MB in all: a larger array as a fixed seeded sample of its elements)")
     ap.add_argument("--launch-check", action="store_true", help="no GPU work: self-launch, rendezvous (gloo), shard + all-gather "
                                                                  "of a stand-in batch, JSON line with value null")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.preset:
         given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
         for k, v in PRESETS[args.preset].items():
@@ -536,12 +590,12 @@ def main():
         raise SystemExit(train_bench(args, world, rank, dev))
     line, pipe = measure(args, world, rank, dev)
     if rank == 0:
-        if world == 1 and not args.no_extra and args.preset in (None, "c2") and args.conv_dtype == "f32" and args.sampler == "ddpm" and not (
+        if world == 1 and args.full and not args.no_extra and args.preset in (None, "c2") and args.conv_dtype == "f32" and args.sampler == "ddpm" and not (
                 args.no_overlap or args.graphs or args.no_sample or args.torch_rng):
             # BASELINE configs[2] and the one-GPU share of configs[3], measured the same way in the same process AFTER the headline's timed
             # region (the line's value / config / dtype stay configs[1]); same random-init networks, their own warm-up
             line["extra_configs"] = extra_configs(args, world, rank, dev, pipe)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             threads = args.cpu_threads or min(os.cpu_count() or 1, 16)
             line["cpu_baseline"] = cpu_baseline(args.timesteps, threads)
         print(json.dumps(line), flush=True)

@@ -1,6 +1,6 @@
 """bf16-activation conv kernel (vsp_conv2d_bf16, io_bf16): pixel-pair staging against the one-pixel tasks (env VSP_BF16_PAIR=0) -- bit-identical
 outputs over every mode / tile variant, and the time of both.  usage: python tools/ab_bf16_pair.py   (runs itself twice as child processes)"""
-import math, os, subprocess, sys
+import math, os, subprocess, sys, tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 CASES = [  # (mode, B, Cin, Cout, H, W, G, dils, hint)
     ("s1", 4, 64, 64, 128, 128, 1, (1,), 0), ("s1", 2, 512, 512, 64, 64, 1, (1,), 0), ("s1", 2, 128, 128, 96, 160, 1, (1,), 4), ("s1", 2, 256, 96, 32, 32, 1, (1,), 1),
@@ -12,7 +12,7 @@ BIG = [("s1", 16, 512, 512, 64, 64, 1, (1,), 0), ("s1", 16, 128, 32, 256, 256, 4
        ("tc", 16, 512, 256, 64, 64, 1, (1,), 0), ("s1", 16, 256, 256, 32, 32, 1, (1,), 0)]
 if os.environ.get("QUICK"):
     BIG = []
-def child(tag):
+def child(path):
     import torch
     from vspbfr_amd import hip_ops as H
     def t(f, n=10):
@@ -44,17 +44,18 @@ def child(tag):
         assert y.dtype == torch.bfloat16
         outs.append(y.float().cpu())
         times.append(t(f) if k >= len(CASES) else 0.0)
-    torch.save({"outs": outs, "times": times}, f"/tmp/ab_bf16_pair_{tag}.pt")
+    torch.save({"outs": outs, "times": times}, path)
 if len(sys.argv) > 1:
     child(sys.argv[1])
 else:
     import torch
     # AB_LIBS=<a.so>,<b.so>: the same comparison between two builds of the library instead of the two staging forms
     libs = os.environ.get("AB_LIBS", "").split(",") if os.environ.get("AB_LIBS") else None
-    for k, (tag, env) in enumerate((("pair", "1"), ("one", "0"))):
-        e = dict(os.environ, VSP_TUNE="1", VSP_BF16_MODW="0", VSP_BF16_PAIR=env) if libs is None else dict(os.environ, VSPBFR_HIP_LIB=libs[k])
-        subprocess.check_call([sys.executable, os.path.abspath(__file__), tag], env=e)
-    a, b = torch.load("/tmp/ab_bf16_pair_pair.pt"), torch.load("/tmp/ab_bf16_pair_one.pt")
+    with tempfile.TemporaryDirectory() as tmp:   # the children's results: private to this run
+        for k, (tag, env) in enumerate((("pair", "1"), ("one", "0"))):
+            e = dict(os.environ, VSP_TUNE="1", VSP_BF16_MODW="0", VSP_BF16_PAIR=env) if libs is None else dict(os.environ, VSPBFR_HIP_LIB=libs[k])
+            subprocess.check_call([sys.executable, os.path.abspath(__file__), os.path.join(tmp, tag + ".pt")], env=e)
+        a, b = torch.load(os.path.join(tmp, "pair.pt")), torch.load(os.path.join(tmp, "one.pt"))
     bad = 0
     for k, (ya, yb) in enumerate(zip(a["outs"], b["outs"])):
         same = torch.equal(ya, yb)

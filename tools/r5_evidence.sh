@@ -5,11 +5,11 @@
 TAG=${1:-final}
 OUT=gpurun_out/r5ev_$TAG
 mkdir -p $OUT
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_default.json
-python bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_default_2.json
-python bench.py --preset c3 2>/dev/null | tail -1 > $OUT/bench_c3.json
-python bench.py --preset c4 2>/dev/null | tail -1 > $OUT/bench_c4.json
-python bench.py --preset c5 2>/dev/null | tail -1 > $OUT/bench_c5.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_default.json
+python bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_default_2.json
+python bench.py --full --preset c3 2>/dev/null | tail -1 > $OUT/bench_c3.json
+python bench.py --full --preset c4 2>/dev/null | tail -1 > $OUT/bench_c4.json
+python bench.py --full --preset c5 2>/dev/null | tail -1 > $OUT/bench_c5.json
 python tools/conv_breakdown.py 2>&1 | grep -v amdgpu.ids > $OUT/conv_breakdown.log
 B=16 T=25 python tools/conv_breakdown_c3.py 2>&1 | grep -v amdgpu.ids > $OUT/conv_breakdown_c3.log
 bash tools/prof_bench.sh r5ev_serial --no-overlap > /dev/null 2>&1

@@ -7,11 +7,11 @@
 TAG=${1:-final}
 OUT=gpurun_out/r6ev_$TAG
 mkdir -p $OUT
-python bench.py --steps 20 2>/dev/null | tail -1 > $OUT/bench_default.json
-python bench.py --steps 20 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_default_2.json
-python bench.py --preset c3 --steps 20 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_c3.json
-python bench.py --preset c4 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_c4.json
-python bench.py --preset c5 2>/dev/null | tail -1 > $OUT/bench_c5.json
+python bench.py --full --steps 20 2>/dev/null | tail -1 > $OUT/bench_default.json
+python bench.py --full --steps 20 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_default_2.json
+python bench.py --full --preset c3 --steps 20 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_c3.json
+python bench.py --full --preset c4 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_c4.json
+python bench.py --full --preset c5 2>/dev/null | tail -1 > $OUT/bench_c5.json
 python tools/conv_breakdown.py 2>&1 | grep -v amdgpu.ids > $OUT/conv_breakdown.log
 python tools/conv_breakdown_c3.py 2>&1 | grep -v amdgpu.ids > $OUT/conv_breakdown_c3.log
 python tools/bench_hidden_cost.py --preset c2 2>/dev/null > $OUT/hidden_cost_c2.json
