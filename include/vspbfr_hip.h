@@ -40,7 +40,7 @@ const char* vsp_last_error(void);
 /* number of HIP devices visible, or a negative VSP_E* code (used by the loader's self-check). */
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
- * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params): lets a binding in
+ * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -631,6 +631,66 @@ int vsp_resize_bilinear_bwd_f32(float* dx, const float* dy, int64_t planes, int 
 #define VSP_NOISE_MAX_SEGMENTS 64
 int vsp_keyed_fill_f32(float* out, int B, const int64_t* seg_elems, const int32_t* seg_ids, int n_seg, uint64_t seed,
                        int64_t image_index0, const int64_t* image_index0_dev, int dist, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training degradations -- the low-quality (LQ) synthesis of the reference's training datasets on the device:
+ * `ImageFolder_restore_free_form.degrade_img` (reference dataset.py:327-373, behind restoration_train.py:454-461) and the same chain
+ * without the haze step in `ImageFolder_restore.__getitem__` (dataset.py:83-127, behind code_diffuser_train.py:365-386).  The
+ * reference runs it on the host with cv2 / numpy, one image at a time; here each stage is ONE launch over a ragged batch of n items
+ * (one item = one LQ image made from gt image `src`), every item with its own parameters in a device table of vsp_degrade_item.
+ *
+ *   gt       (B, 3, H, W) fp32 in [0, 1]; blurred / out (n, 3, H, W) fp32
+ *   lq       uint8, item i's three planes of dh*dw samples at element offset pix_off (channel order of the gt)
+ *   noise / pre (optional) fp32, item i's (dh, dw, 3) values at element offset pix_off (numpy's randn(h, w, 3) order)
+ *   work     uint8, item i's JPEG planes at byte offset jpg_off: Y (ph*pw), Cb, Cr (ph/2*pw/2 each), ph / pw = dh / dw rounded up to 16
+ * The caller sizes every buffer from the table it uploads; the kernels clamp what they derive from an entry but do not check
+ * offsets against buffer sizes (they cannot see them): vspbfr_amd/degrade.py builds and checks the table.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_DEGRADE_MAX_KSIZE 41      /* blur taps per side (odd) */
+#define VSP_DEGRADE_MAX_SIZE 2048     /* image side, gt and downsampled */
+#define VSP_DEGRADE_MAX_ITEMS 1024    /* items per launch */
+#define VSP_DEGRADE_HAZE 1            /* flags: x * alpha + (1 - alpha) after the blur (dataset.py:341-344) */
+#define VSP_DEGRADE_GREY 2            /* flags: cv2 BGR2GRAY of the final LQ (dataset.py:303-308) */
+#define VSP_DEGRADE_NOISE_KEY 0x44475244u /* xor-ed into the low key word of the noise draws ("DGRD") */
+
+typedef struct vsp_degrade_item {
+  int64_t tap_off;   /* float offset of the ksize*ksize taps (row-major, correlation order) in `taps` */
+  int64_t pix_off;   /* element offset of the item in lq / noise / pre */
+  int64_t jpg_off;   /* byte offset of the item's JPEG planes in `work` */
+  int64_t sample;    /* global sample index (noise key) */
+  int32_t src;       /* gt image of the batch */
+  int32_t ksize;     /* blur taps per side, odd, <= VSP_DEGRADE_MAX_KSIZE */
+  int32_t dh, dw;    /* downsampled size: (int(h // scale), int(w // scale)) (dataset.py:347-348) */
+  int32_t quality;   /* JPEG quality 1..100 (my_degradations.py:681-710) */
+  int32_t flags;     /* VSP_DEGRADE_HAZE | VSP_DEGRADE_GREY */
+  int32_t mcu0;      /* index of the item's first 16x16 MCU in the batch (running sum of ceil(dh/16) * ceil(dw/16)) */
+  int32_t slot;      /* LQ slot of the sample, 0..3 (noise key) */
+  float alpha;       /* haze alpha */
+  float sigma;       /* noise standard deviation on the 0..255 scale (my_degradations.py:386-400) */
+} vsp_degrade_item;
+
+/* gt: out (B, 3, H, W) = hwc (B, H, W, 3) uint8 / 255 (dataset.py:277 `np.array(img) / 255`), or = in (B, 3, H, W) fp32 (in == out
+ * allowed); exactly one of hwc / in.  grey (device int32 [B] or NULL): cv2 BGR2GRAY of image b where grey[b] != 0 (dataset.py:303-311). */
+int vsp_degrade_gt_f32(float* out, const uint8_t* hwc, const float* in, const int32_t* grey, int B, int H, int W, vsp_stream_t stream);
+/* blur: blurred[i] = cv2.filter2D(gt[src_i], -1, taps_i) (correlation, anchor at the centre, BORDER_REFLECT_101; dataset.py:337-338,
+ * my_degradations.py:295-356), then the haze of dataset.py:341-344 where flagged. */
+int vsp_degrade_blur_f32(float* out, const float* gt, const float* taps, const vsp_degrade_item* items, int n, int B, int H, int W,
+                         vsp_stream_t stream);
+/* down: cv2.resize(blurred[i], (dw, dh), INTER_LINEAR) (dataset.py:347-348), + noise * sigma / 255, clip to [0, 1] (my_degradations.py
+ * :386-400, :483-492), saturate_cast to uint8 (round half to even) as cv2.imencode does (:681-710).  noise: injected values, or NULL
+ * for  Philox4x32-10 (key = (seed_lo ^ VSP_DEGRADE_NOISE_KEY, seed_hi), counter = (e / 4, step << 2 | slot, sample_lo, sample_hi))
+ * with Box-Muller as vsp_keyed_fill_f32, element e of the item's (dh, dw, 3) draw.  pre (optional): the resized values before the
+ * noise.  max_pixels >= every item's dh * dw. */
+int vsp_degrade_down_u8(uint8_t* lq, float* pre, const float* blurred, const float* noise, const vsp_degrade_item* items, int n, int H,
+                        int W, int max_pixels, uint64_t seed, int64_t step, vsp_stream_t stream);
+/* jpeg: in place, the pixel values of cv2.imdecode(cv2.imencode('.jpg', img, quality)) (my_degradations.py:681-710) at libjpeg's
+ * defaults -- 4:2:0, ISLOW DCT, baseline quality tables, fancy upsampling -- with channel 0 read as blue (cv2's BGR).  Bit-exact.
+ * Two launches: per-MCU transform into `work`, then upsampling + colour back into lq.  total_mcus = sum of the items' MCUs. */
+int vsp_degrade_jpeg_u8(uint8_t* lq, uint8_t* work, const vsp_degrade_item* items, int n, int total_mcus, int max_pixels,
+                        vsp_stream_t stream);
+/* up: out[i] = np.clip(round(cv2.resize(lq_i / 255, (W, H), INTER_LINEAR) * 255), 0, 255) / 255 (dataset.py:356, :370), then cv2
+ * BGR2GRAY where flagged (dataset.py:303-306). */
+int vsp_degrade_up_f32(float* out, const uint8_t* lq, const vsp_degrade_item* items, int n, int H, int W, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

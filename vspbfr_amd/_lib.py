@@ -98,6 +98,14 @@ class GemmParams(C.Structure):
     ]
 
 
+class DegradeItem(C.Structure):
+    _fields_ = [("tap_off", C.c_int64), ("pix_off", C.c_int64), ("jpg_off", C.c_int64), ("sample", C.c_int64)] + [
+        (n, C.c_int32) for n in ("src", "ksize", "dh", "dw", "quality", "flags", "mcu0", "slot")] + [("alpha", C.c_float), ("sigma", C.c_float)]
+
+
+DEGRADE_HAZE, DEGRADE_GREY = 1, 2            # vsp_degrade_item.flags (include/vspbfr_hip.h VSP_DEGRADE_*)
+DEGRADE_MAX_KSIZE, DEGRADE_MAX_SIZE, DEGRADE_MAX_ITEMS = 41, 2048, 1024
+
 _i, _i64, _f, _p = C.c_int, C.c_int64, C.c_float, C.c_void_p
 
 # name -> argtypes: every symbol include/vspbfr_hip.h declares (tests/test_abi.py cross-checks against the header)
@@ -172,6 +180,11 @@ SIGNATURES = {
     "vsp_modulate_weight_bf16": [_p, _p, _p, _i, _i64, _i, _i, _i, _p],
     "vsp_conv2d_winograd_chunk": [],
     "vsp_conv2d_winograd_mbw": [_i],
+    "vsp_degrade_gt_f32": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "vsp_degrade_blur_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "vsp_degrade_down_u8": [_p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, _i64, _p],
+    "vsp_degrade_jpeg_u8": [_p, _p, _p, _i, _i, _i, _p],
+    "vsp_degrade_up_f32": [_p, _p, _p, _i, _i, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
@@ -200,7 +213,7 @@ def _load():
     if lib.vsp_abi_version() != ABI_VERSION:
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
-                      (5, ConvWgradParams)):
+                      (5, ConvWgradParams), (6, DegradeItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -1523,6 +1523,77 @@ def plane_dot(a, b):
     check(lib.vsp_plane_dot_f32(_ptr(out), _ptr(a), _ptr(b), planes, a.numel() // max(planes, 1), _stream()), "plane_dot")
     return out
 
+# ----------------------------------------------------------------------------------------------- training degradations
+# Thin wrappers of the vsp_degrade_* stages (csrc/degrade.hip).  `items` is a device uint8 tensor holding n vsp_degrade_item structs and
+# `taps` a device fp32 tensor, both uploaded by vspbfr_amd.degrade.DegradePlan, which also sizes the ragged buffers passed here.
+def _u8(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous CUDA uint8 tensor")
+    return t
+
+
+def degrade_gt(hwc=None, src=None, grey=None, out=None):
+    """(B, H, W, 3) uint8 -> (B, 3, H, W) fp32 / 255, or (B, 3, H, W) fp32 -> out (may be src itself); grey: device int32 (B,) flags of
+    the images to turn grey (cv2 BGR2GRAY weights)."""
+    if (hwc is None) == (src is None):
+        raise RuntimeError("degrade_gt: exactly one of hwc / src")
+    if hwc is not None:
+        _u8(hwc, "hwc")
+        if hwc.dim() != 4 or hwc.shape[3] != 3:
+            raise RuntimeError("degrade_gt: hwc must be (B, H, W, 3)")
+        B, Hh, Ww = hwc.shape[:3]
+    else:
+        _req(src, "src")
+        if src.dim() != 4 or src.shape[1] != 3:
+            raise RuntimeError("degrade_gt: src must be (B, 3, H, W)")
+        B, Hh, Ww = src.shape[0], src.shape[2], src.shape[3]
+    if out is None:
+        out = torch.empty((B, 3, Hh, Ww), device=(hwc if hwc is not None else src).device, dtype=torch.float32)
+    elif tuple(_req(out, "out").shape) != (B, 3, Hh, Ww):
+        raise RuntimeError("degrade_gt: out shape")
+    if grey is not None and (not grey.is_cuda or grey.dtype != torch.int32 or grey.numel() != B):
+        raise RuntimeError("degrade_gt: grey must be a CUDA int32 tensor of B flags")
+    check(lib.vsp_degrade_gt_f32(_ptr(out), _ptr(hwc), _ptr(src), _ptr(grey), B, Hh, Ww, _stream()), "degrade_gt")
+    return out
+
+
+def degrade_blur(gt, taps, items, n):
+    """(B, 3, H, W) -> (n, 3, H, W): item i = gt[src_i] correlated with its taps (reflect-101), haze where flagged."""
+    gt, taps = _req(gt, "gt"), _req(taps, "taps")
+    B, _, Hh, Ww = gt.shape
+    out = torch.empty((n, 3, Hh, Ww), device=gt.device, dtype=torch.float32)
+    check(lib.vsp_degrade_blur_f32(_ptr(out), _ptr(gt), _ptr(taps), _ptr(_u8(items, "items")), n, B, Hh, Ww, _stream()), "degrade_blur")
+    return out
+
+
+def degrade_down(blurred, items, n, lq_elems, max_pixels, seed, step, noise=None, pre=False):
+    """(n, 3, H, W) -> ragged uint8 (lq_elems,) of resized + noisy + rounded images; with pre=True also the fp32 resized values before
+    the noise (ragged (dh, dw, 3) per item).  noise: injected ragged fp32 (lq_elems,) or None for the keyed Philox draw."""
+    blurred = _req(blurred, "blurred")
+    lq = torch.empty(lq_elems, device=blurred.device, dtype=torch.uint8)
+    pre_t = torch.empty(lq_elems, device=blurred.device, dtype=torch.float32) if pre else None
+    if noise is not None and (_req(noise, "noise").numel() != lq_elems):
+        raise RuntimeError("degrade_down: noise must hold lq_elems values")
+    check(lib.vsp_degrade_down_u8(_ptr(lq), _ptr(pre_t), _ptr(blurred), _ptr(noise), _ptr(_u8(items, "items")), n, blurred.shape[2],
+                                  blurred.shape[3], max_pixels, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(step), _stream()),
+          "degrade_down")
+    return (lq, pre_t) if pre else lq
+
+
+def degrade_jpeg(lq, items, n, total_mcus, work_bytes, max_pixels):
+    """In place: the JPEG round trip of every item of the ragged uint8 image buffer."""
+    work = torch.empty(max(int(work_bytes), 1), device=lq.device, dtype=torch.uint8)
+    check(lib.vsp_degrade_jpeg_u8(_ptr(_u8(lq, "lq")), _ptr(work), _ptr(_u8(items, "items")), n, total_mcus, max_pixels, _stream()),
+          "degrade_jpeg")
+    return lq
+
+
+def degrade_up(lq, items, n, Hh, Ww):
+    """ragged uint8 -> (n, 3, H, W) fp32 multiples of 1/255 (grey where flagged)."""
+    out = torch.empty((n, 3, Hh, Ww), device=lq.device, dtype=torch.float32)
+    check(lib.vsp_degrade_up_f32(_ptr(out), _ptr(_u8(lq, "lq")), _ptr(_u8(items, "items")), n, Hh, Ww, _stream()), "degrade_up")
+    return out
+
 
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
