@@ -111,13 +111,15 @@ def test_operand_device_refusal_logic():
         H.fused_bias_act(a, m, torch.zeros(0), 3, 0, 0.2, 1.0)
 
 
-def test_tuned_table_winograd_entries_name_eligible_layers():
+def test_tuned_table_winograd_entries_name_eligible_layers(monkeypatch):
     """Every shape key of vspbfr_amd/conv_tune.json that names a Winograd kernel describes a layer that kernel's eligibility rule accepts
     (a key the rule refuses would silently fall back at run time and the table's measurement would no longer describe what runs): the
-    fused F(4x4) kernel incl. its dilation-group launches (G = 4, dilations 1 / 2 / 4 / 8 over one shared input), the F(4x4) pair, F(2x2)."""
+    fused F(4x4) kernel incl. its dilation-group launches (G = 4, dilations 1 / 2 / 4 / 8 over one shared input), the F(4x4) pair, F(2x2);
+    and hip_ops.conv_route sends the key to that kernel."""
     import json
 
     from vspbfr_amd import hip_ops as H
+    monkeypatch.setattr(H, "BF16_CONV", False)
     table = json.load(open(os.path.join(ROOT, "vspbfr_amd", "conv_tune.json")))
     seen = {"winograd": 0, "winograd4": 0, "winograd4f": 0}
     for key, val in table.items():
@@ -137,6 +139,8 @@ def test_tuned_table_winograd_entries_name_eligible_layers():
         else:
             ok = H.winograd_eligible(pc, Hh, Ww, OH, OW)
         assert ok, (key, val)
+        r = H.conv_route(pc, B, Hh, Ww, OH, OW, in_shift=shift is not None)
+        assert r.key == key and r.family == {"winograd": "wino", "winograd4": "wino4", "winograd4f": "wino4f"}[val], (key, val, r)
         seen[val] += 1
     assert seen["winograd4f"] >= 20 and seen["winograd4"] >= 3 and seen["winograd"] >= 10, seen
     assert sum(1 for k, v in table.items() if v == "winograd4f" and k.split(",")[4] == "4") >= 8      # the dilation-group launches of DESIGN 6.6

@@ -568,7 +568,7 @@ def test_conv2d_winograd4_refusals(H):
     x = dev(torch.randn(1, 8, 16, 32))
     w = dev(torch.randn(64, 8, 3, 3))
     pc = H.PackedConv(H.pack_weight(w), 1, 64, 8, 3, 3, 1, (1,), (1,))
-    u4 = pc.winograd4_weight()
+    u4 = pc.form("wino4")
     assert u4.numel() == _lib.lib.vsp_winograd4_weight_floats(8, 64)
     p = _lib.ConvParams()
     out = torch.empty(1, 64, 16, 32, device=DEV)

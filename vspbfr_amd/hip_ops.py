@@ -6,6 +6,7 @@ there is no CPU path (the reference's own CPU branch lives in oracle/, test-only
 """
 import ctypes as C
 import math
+from collections import namedtuple
 
 import os
 
@@ -123,6 +124,12 @@ RESBLOCK_ONE_NODE = tune_env("VSP_RESBLOCK_ONE_NODE", "1") != "0"
 def conv_key(B, Cin, H, W, pc, OH, OW):
     return f"{B},{Cin},{H},{W},{pc.G},{pc.cout_g},{pc.kh},{pc.kw},{pc.stride},{pc.dil[0]},{OH},{OW}" + (
         f",g{pc.x_group_stride}" if pc.x_group_stride else "") + (",q" if pc.dil_by_input_quarter else "")
+
+
+def _tuned(table, key, default=0):
+    """The table's entry for this shape key, else that of the same layer at batch 8 (the batch the tables were measured at)."""
+    v = table.get(key)
+    return v if v is not None else table.get("8" + key[key.index(","):], default)
 
 
 def _stream():
@@ -317,8 +324,7 @@ class PackedConv:
     """A convolution weight in the kernel's layout Wp[g][tap][ci][co_g] (include/vspbfr_hip.h) plus its geometry.
     Built once per device on first use (pack_weight below; cached on the owning module)."""
 
-    __slots__ = ("w", "G", "cout_g", "cin", "kh", "kw", "stride", "dil", "pad_y", "pad_x", "x_group_stride", "dil_by_input_quarter",
-                 "_wino", "_wino4", "_wino4f", "_bf16", "_bf16x3", "_bf16rv", "_bf16dg")
+    __slots__ = ("w", "G", "cout_g", "cin", "kh", "kw", "stride", "dil", "pad_y", "pad_x", "x_group_stride", "dil_by_input_quarter", "_forms")
 
     def __init__(self, w, G, cout_g, cin, kh, kw, stride=1, dil=(1,), pad_y=(0,), pad_x=None, x_group_stride=0, dil_by_input_quarter=False):
         self.w, self.G, self.cout_g, self.cin, self.kh, self.kw = w, G, cout_g, cin, kh, kw
@@ -331,68 +337,19 @@ class PackedConv:
         self.dil = rep(dil, 1)          # one value = the same geometry for every group
         self.pad_y = rep(pad_y, 0)
         self.pad_x = rep(pad_y if pad_x is None else pad_x, 0)
-        self._wino = None
-        self._wino4 = None
-        self._wino4f = None
-        self._bf16 = None
-        self._bf16x3 = None
-        self._bf16rv = None
-        self._bf16dg = None
+        self._forms = {}
 
     @property
     def cout(self):
         return self.G * self.cout_g
 
-    def winograd_weight(self):
-        """U = G g G^T (16, Cin, Cout), built on first use and kept with the packed weight."""
-        if self._wino is None:
+    def form(self, name):
+        """The weight in the layout of kernel family `name` (a key of WEIGHT_FORMS), built on first use and kept with the packed weight."""
+        f = self._forms.get(name)
+        if f is None:
             with torch.no_grad():
-                self._wino = winograd_weight(self.w)
-        return self._wino
-
-
-    def winograd4_weight(self):
-        """U = G g G^T of F(4x4,3x3) (36, Cin, Cout) in the fragment order of vsp_conv2d_winograd4_f32, built on first use."""
-        if self._wino4 is None:
-            with torch.no_grad():
-                self._wino4 = winograd4_weight(self.w)
-        return self._wino4
-
-    def winograd4f_weight(self):
-        """U = G g G^T of F(4x4,3x3) in the order of the fused kernel vsp_conv2d_winograd4f_f32, built on first use."""
-        if self._wino4f is None:
-            with torch.no_grad():
-                self._wino4f = winograd4f_weight(self.w)
-        return self._wino4f
-
-    def bf16_weight(self):
-        """The weight rounded to bf16 in the LDS-image order of vsp_conv2d_bf16, built on first use."""
-        if self._bf16 is None:
-            with torch.no_grad():
-                self._bf16 = bf16_weight(self.w)
-        return self._bf16
-
-
-    def bf16rv_weight(self):
-        """The weight rounded to bf16 in the fragment order of vsp_conv2d_bf16rv, built on first use."""
-        if self._bf16rv is None:
-            with torch.no_grad():
-                self._bf16rv = bf16rv_weight(self.w)
-        return self._bf16rv
-
-    def bf16dg_weight(self):
-        """The fp32 weight in the A-fragment order of vsp_conv2d_bf16dg, built on first use."""
-        if self._bf16dg is None:
-            with torch.no_grad():
-                self._bf16dg = bf16dg_weight(self.w)
-        return self._bf16dg
-
-    def bf16x3_weight(self):
-        """hi + lo bf16 parts of the weight in the LDS-image order of vsp_conv2d_bf16x3, built on first use."""
-        if self._bf16x3 is None:
-            with torch.no_grad():
-                self._bf16x3 = bf16x3_weight(self.w)
-        return self._bf16x3
+                f = self._forms[name] = WEIGHT_FORMS[name](self.w)
+        return f
 
 
 # "bf16 kernels" configuration (BASELINE configs[2]): eligible convolutions run on vsp_conv2d_bf16 (bf16 MFMA, fp32
@@ -522,35 +479,6 @@ def bf16rv_profitable(pc, H, W):
     return pc.cin <= 256 and H * W >= 128 * 128
 
 
-def _bf16rv_call(p, pc, keep, forced):
-    """One launch of vsp_conv2d_bf16rv on the filled parameter block; False = the entry does not serve it (alignment): the caller
-    goes on to vsp_conv2d_bf16."""
-    bw = pc.bf16rv_weight()
-    w0, h0 = p.w, p.tile_hint
-    p.w, p.tile_hint = bw.data_ptr(), (p.tile_hint if forced else 0)
-    rc = lib.vsp_conv2d_bf16rv(C.byref(p), _stream())
-    if rc == -3 and not forced:
-        p.w, p.tile_hint = w0, h0
-        return False
-    check(rc, "conv2d_bf16rv")
-    keep.append(bw)
-    return True
-
-
-def _bf16dg_call(p, pc, keep, forced):
-    """One launch of vsp_conv2d_bf16dg; False = the entry does not serve it (alignment): the caller goes on to the other bf16 kernels."""
-    bw = pc.bf16dg_weight()
-    w0, h0 = p.w, p.tile_hint
-    p.w, p.tile_hint = bw.data_ptr(), 0
-    rc = lib.vsp_conv2d_bf16dg(C.byref(p), _stream())
-    if rc == -3 and not forced:
-        p.w, p.tile_hint = w0, h0
-        return False
-    check(rc, "conv2d_bf16dg")
-    keep.append(bw)
-    return True
-
-
 def bf16x3_weight(wp):
     """packed weights (G, 9, Cin, cout_g) fp32 -> [group][chunk][part 2][tap][octet 2][co_pad][8] bf16 with part 0 = bf16(W),
     part 1 = bf16(W - float(bf16(W))) (vsp_conv2d_bf16x3)."""
@@ -666,63 +594,211 @@ def conv2d_out_size(H, W, pc):
     return oh, ow
 
 
+ConvRoute = namedtuple("ConvRoute", "family hint io_bf16 named key")
+
+
+def conv_route(pc, B, H, W, OH, OW, transposed=False, out_stride=(1, 1), out_offset=(0, 0), in_shift=False, x_dtype=torch.float32,
+               out_dtype=None, winograd=None, bf16=None, tile_hint=0, wino_form=0):
+    """Which kernel family serves a conv2d_packed launch: pure host logic on plain values (no library call, no device memory), reading the
+    tuned tables and module switches at call time.  `in_shift`: whether the launch has one; `out_dtype`: that of the caller's `out`, None
+    without one; `winograd` / `bf16` / `tile_hint` / `wino_form`: the caller's (see conv2d_packed).  A family named by the caller on a layer
+    its eligibility rule refuses raises.  -> ConvRoute(family, hint, io_bf16, named, key): `family` the launcher and profiler label,
+    `hint` the tile_hint it starts with, `io_bf16` bf16 activations, `named` the caller's `winograd` / `bf16` named the family, `key` the
+    shape key of the tables.  In order:
+    1. tile_hint 0 takes the TUNE entry as a preference (negative hint: the cost model decides where that tile cannot serve the call).
+    2. bf16: the caller's `bf16`; None = BF16_CONV on a bf16_eligible, bf16_profitable layer when no Winograd kernel was asked for
+       (BF16_CONV "x3": the subset where the split form wins).  "rv" / "dg" -> bf16rv / bf16dg (bf16 activations required, hint = the
+       caller's); "x3" -> bf16x3; with bf16 activations and neither a caller's variant nor BF16_FORCE: bf16dg on the dilation-group
+       launches it serves (BF16_DG), else bf16rv where eligible and profitable (BF16_RV); else bf16.  hint = the caller's variant, else
+       BF16_FORCE, else BF16_TUNE / BF16X3_TUNE (the automatic bf16rv / bf16dg pick their own and keep it for their fall-back to bf16).
+    3. Winograd: the caller's `winograd`; None = the WINO table on a winograd_eligible layer without a tile preference.  5 -> wino4f where
+       winograd4f_eligible (else a named 5 raises, an unnamed one takes wino), 4 -> wino4 where winograd4_eligible (else wino).
+       hint = `wino_form`, the F(2x2) form.
+    4. direct, tconv when transposed, with the hint of step 1."""
+    key = conv_key(B, pc.cin, H, W, pc, OH, OW) + (",t" if transposed else "") + (",s" if in_shift else "")
+    geo = (pc, H, W, OH, OW, transposed, out_stride, out_offset)
+    shift = True if in_shift else None
+    pref = tile_hint or -_tuned(TUNE, key)
+    named = bf16 is not None
+    x3 = bf16 == "x3" or (not named and BF16_CONV == "x3")
+    if not named:
+        bf16 = (bool(BF16_CONV) and not winograd and bf16_eligible(*geo) and bf16_profitable(pc, H, W, OH, OW, transposed) and (
+            # split precision: doubled LDS images -- the layers where it beats the tuned fp32 kernels (tools/conv_breakdown.py)
+            not x3 or (W >= 32 if transposed else pc.stride == 1 or (pc.stride == 2 and pc.G == 1 and OW >= 32))))
+    elif bf16 and not bf16_eligible(*geo):
+        raise RuntimeError("conv2d: this layer is not eligible for the bf16 kernel (see bf16_eligible)")
+    if bf16:
+        io = not x3 and (x_dtype == BF or (ACT_BF16 and out_dtype is None)) and out_dtype in (None, BF)
+        if bf16 in ("rv", "dg"):
+            if bf16 == "rv" and not bf16rv_eligible(*geo):
+                raise RuntimeError("conv2d: this layer is not eligible for the row-vector bf16 kernel (see bf16rv_eligible)")
+            if bf16 == "dg" and not bf16dg_eligible(*geo, shift):
+                raise RuntimeError("conv2d: this layer is not eligible for the dilation-group bf16 kernel (see bf16dg_eligible)")
+            if not io:
+                raise RuntimeError("conv2d: bf16='rv' names the row-vector kernel, which reads and writes bf16 activations: pass a bf16 input "
+                                   "(and output) or switch ACT_BF16 on")
+            return ConvRoute("bf16" + bf16, max(tile_hint, 0), True, True, key)
+        own = max(tile_hint, 0)
+        hint = own or BF16_FORCE or _tuned(BF16X3_TUNE if x3 else BF16_TUNE, key)
+        if x3:
+            return ConvRoute("bf16x3", hint, False, named, key)
+        if io and not own and not BF16_FORCE:
+            if BF16_DG and pc.G > 1 and bf16dg_eligible(*geo, shift):
+                return ConvRoute("bf16dg", hint, True, False, key)
+            if BF16_RV and bf16rv_eligible(*geo) and bf16rv_profitable(pc, H, W):
+                return ConvRoute("bf16rv", hint, True, False, key)
+        return ConvRoute("bf16", hint, io, named, key)
+    named = winograd is not None
+    if not named:
+        winograd = not pref and winograd_eligible(*geo) and _tuned(WINO, key, False)
+    elif winograd and not winograd_eligible(*geo):
+        raise RuntimeError("conv2d: this layer is not eligible for the Winograd kernel (3x3, stride 1, dilation 1, pad 1, G = 1)")
+    if winograd == 5:
+        if winograd4f_eligible(*geo, shift):
+            return ConvRoute("wino4f", wino_form, False, named, key)
+        if named:
+            raise RuntimeError("conv2d: this launch is not eligible for the fused F(4x4,3x3) kernel (winograd4f_eligible: one group or up to four "
+                               "dilation groups over one shared input, 3x3 / stride 1 / padding = dilation in {1, 2, 4, 8}, H and W multiples of "
+                               "4 x dilation, no affine shift, Cin % 8 == 0 up to 512, W >= 16)")
+    elif winograd == 4 and winograd4_eligible(*geo, shift):
+        return ConvRoute("wino4", wino_form, False, named, key)
+    if winograd:
+        return ConvRoute("wino", wino_form, False, named, key)
+    return ConvRoute("tconv" if transposed else "direct", pref, False, False, key)
+
+
+# ---- one launcher per kernel family: (filled ConvParams, PackedConv, keep-alive list, named, in_scale) -> the family that ran.  Each owns its
+# VSP_ENOTSUP (-3) fall-back; a named fused F(4x4), row-vector or dilation-group launch raises instead (the pair and bf16x3 fall back either way).
+def _set_weight(p, keep, w):
+    keep.append(w)
+    p.w = w.data_ptr()
+
+
+def _force_retry(entry, p):
+    """One launch of `entry`; when the variant BF16_FORCE imposes (tuner) does not serve it, another with the library's own choice."""
+    rc = entry(p)
+    if rc != 0 and BF16_FORCE and p.tile_hint == BF16_FORCE:
+        p.tile_hint = 0
+        rc = entry(p)
+    return rc
+
+
+def _launch_f32(p, pc, keep, named, in_scale):
+    check(lib.vsp_conv2d_f32(C.byref(p), _stream()), "conv2d")
+    return "tconv" if p.transposed else "direct"
+
+
+def _launch_wino(p, pc, keep, named, in_scale):
+    _set_weight(p, keep, pc.form("wino"))
+    check(lib.vsp_conv2d_winograd_f32(C.byref(p), _stream()), "conv2d_winograd")
+    return "wino"
+
+
+def _launch_wino4(p, pc, keep, named, in_scale):
+    _set_weight(p, keep, pc.form("wino4"))
+    nfl = lib.vsp_conv2d_winograd4_work_floats(C.byref(p))
+    work = torch.empty(nfl, device=pc.w.device, dtype=torch.float32)   # V = B^T d B in fragment order (2.25 x the input)
+    keep.append(work)
+    rc = lib.vsp_conv2d_winograd4_f32(C.byref(p), _ptr(work), nfl, _stream())
+    if rc == -3:   # VSP_ENOTSUP: alignment of an operand plane -> F(2x2,3x3)
+        return _launch_wino(p, pc, keep, named, in_scale)
+    check(rc, "conv2d_winograd4")
+    return "wino4"
+
+
+def _launch_wino4f(p, pc, keep, named, in_scale):
+    _set_weight(p, keep, pc.form("wino4f"))
+    rc = lib.vsp_conv2d_winograd4f_f32(C.byref(p), _stream())
+    if rc == -3 and not named:   # VSP_ENOTSUP: alignment of an operand plane -> F(2x2,3x3)
+        return _launch_wino(p, pc, keep, named, in_scale)
+    check(rc, "conv2d_winograd4f")
+    return "wino4f"
+
+
+def _launch_bf16x3(p, pc, keep, named, in_scale):
+    _set_weight(p, keep, pc.form("bf16x3"))
+    rc = _force_retry(lambda q: lib.vsp_conv2d_bf16x3(C.byref(q), _stream()), p)
+    if rc == -3:   # VSP_ENOTSUP: the doubled LDS images of this shape do not fit (small stride-2 maps) -> the fp32 kernel
+        p.w = pc.w.data_ptr()
+        return _launch_f32(p, pc, keep, named, in_scale)
+    check(rc, "conv2d_bf16x3")
+    return "bf16x3"
+
+
+def _launch_bf16(p, pc, keep, named, in_scale):
+    # a modulated layer with bf16 activations (per-sample style, no shift, even rows): the style goes into per-image weights (the
+    # reference's fused form) and the kernel's staging becomes a copy (conv_bf16.hip NOSC)
+    if (BF16_MODW and p.io_bf16 and p.in_scale_bstride and p.in_shift is None and p.x_group_stride == 0 and p.W % 2 == 0
+            and in_scale.dim() == 2 and in_scale.shape == (p.B, p.Cin) and p.x % 4 == 0):
+        bw, wbytes = bf16_modulated_weight(pc, in_scale)
+        p.in_scale, p.in_scale_bstride, p.w_bstride = None, 0, wbytes
+    else:
+        bw = pc.form("bf16")
+    _set_weight(p, keep, bw)
+
+    def entry(q):
+        rc = lib.vsp_conv2d_bf16(C.byref(q), _stream())
+        if rc == -3 and q.w_bstride:   # VSP_ENOTSUP: this tile's patch plane is too large for the copy-only staging -> shared weights + style scale
+            _set_weight(q, keep, pc.form("bf16"))
+            q.w_bstride, q.in_scale, q.in_scale_bstride = 0, in_scale.data_ptr(), q.Cin
+            rc = lib.vsp_conv2d_bf16(C.byref(q), _stream())
+        return rc
+    check(_force_retry(entry, p), "conv2d_bf16")
+    return "bf16"
+
+
+def _launch_bf16rv(p, pc, keep, named, in_scale):
+    hint = p.tile_hint
+    if not named:   # automatic: the kernel's own variant; `hint` is the one of vsp_conv2d_bf16
+        p.tile_hint = 0
+    _set_weight(p, keep, pc.form("bf16rv"))
+    rc = lib.vsp_conv2d_bf16rv(C.byref(p), _stream())
+    if rc == -3 and not named:   # VSP_ENOTSUP: alignment -> vsp_conv2d_bf16
+        p.tile_hint = hint
+        return _launch_bf16(p, pc, keep, named, in_scale)
+    check(rc, "conv2d_bf16rv")
+    return "bf16rv"
+
+
+def _launch_bf16dg(p, pc, keep, named, in_scale):
+    _set_weight(p, keep, pc.form("bf16dg"))
+    rc = lib.vsp_conv2d_bf16dg(C.byref(p), _stream())   # (no variants: tile_hint is not read)
+    if rc == -3 and not named:   # VSP_ENOTSUP: alignment -> vsp_conv2d_bf16
+        return _launch_bf16(p, pc, keep, named, in_scale)
+    check(rc, "conv2d_bf16dg")
+    return "bf16dg"
+
+
+_LAUNCH = {"direct": _launch_f32, "tconv": _launch_f32, "wino": _launch_wino, "wino4": _launch_wino4, "wino4f": _launch_wino4f,
+           "bf16": _launch_bf16, "bf16x3": _launch_bf16x3, "bf16rv": _launch_bf16rv, "bf16dg": _launch_bf16dg}
+
+
 def conv2d_packed(x, pc, out=None, out_hw=None, y_coff=0, out_stride=(1, 1), out_offset=(0, 0), in_scale=None,
                   in_scale_per_sample=True, in_shift=None, out_scale=None, ch_scale=None, ch_bias=None, act1=False,
                   bias1=None, noise=None, noise_w=None, act2=0, bias2=None, prelu=None, slope2=0.2, gain2=SQRT2, res1=None,
                   res2=None, res_coff=0, n_out=None, tile_hint=0, transposed=False, winograd=None, bf16=None, wino_form=0):
-    """Launch vsp_conv2d_f32.  `out` (B, y_ch, y_h, y_w) is allocated when None.  `n_out` = (OH, OW) positions to
-    compute (defaults to the standard conv output size).  `winograd`: True / False forces / forbids the F(2x2,3x3) kernel
-    (vsp_conv2d_winograd_f32) on an eligible layer; None = what the tuned table says for this shape; `wino_form` names the F(2x2) kernel
-    form (0 automatic, 1 task list, 2 row owner, 3 register-resident U: include/vspbfr_hip.h, tests / tuning).  `bf16`: True runs the
-    layer on vsp_conv2d_bf16 (tile_hint = its variant), None = the module switch BF16_CONV on eligible layers."""
+    """One convolution on the kernel family conv_route picks.  `out` (B, y_ch, y_h, y_w) is allocated when None.  `n_out` = (OH, OW) positions
+    to compute (defaults to the standard conv output size).  `winograd`: True / False forces / forbids the F(2x2,3x3) kernel
+    (vsp_conv2d_winograd_f32) on an eligible layer, 4 / 5 name the F(4x4,3x3) pair / fused kernel; None = what the tuned table says for this
+    shape; `wino_form` names the F(2x2) kernel form (0 automatic, 1 task list, 2 row owner, 3 register-resident U: include/vspbfr_hip.h,
+    tests / tuning).  `bf16`: True runs the layer on vsp_conv2d_bf16 (tile_hint = its variant), "x3" / "rv" / "dg" on its split-precision /
+    row-vector / dilation-group forms, None = the module switch BF16_CONV on eligible layers."""
     x = _req(x, "x", bf16_ok=True)
     B, x_ch, H, W = x.shape
     Cin = pc.cin
     if (pc.G - 1) * pc.x_group_stride + Cin != x_ch:
         raise RuntimeError(f"conv2d: input has {x_ch} channels, weight expects {(pc.G - 1) * pc.x_group_stride + Cin}")
     OH, OW = n_out if n_out is not None else ((H + 1, W + 1) if transposed else conv2d_out_size(H, W, pc))
-    # ---- which kernel family serves this launch (decided before anything is allocated: it fixes the activation dtype)
-    key = conv_key(B, Cin, H, W, pc, OH, OW) + (",t" if transposed else "") + (",s" if in_shift is not None else "")
-    if tile_hint == 0 and TUNE:
-        pref = TUNE.get(key, 0)
-        if pref == 0 and B != 8:  # the table was measured at batch 8; large layers keep their tile at other batches
-            pref = TUNE.get("8" + key[key.index(","):], 0)
-        tile_hint = -pref  # negative = preference: falls back to the cost model when it cannot serve this call's operands
-    bf_ok = bf16_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset)
-    x3 = bf16 == "x3" or (bf16 is None and BF16_CONV == "x3")
-    rv = None          # the row-vector-K kernel (vsp_conv2d_bf16rv): "rv" forces it, None = where it is eligible and measured faster
-    dg = None          # the dilation-group kernel (vsp_conv2d_bf16dg): "dg" forces it, None = the dilation-group launches it serves
-    if bf16 == "rv":
-        bf16, rv = True, True
-    if bf16 == "dg":
-        bf16, dg = True, True
-    if bf16 is None:
-        bf16 = bool(BF16_CONV) and bf_ok and not winograd and bf16_profitable(pc, H, W, OH, OW, transposed)
-        if x3 and bf16:  # split precision: doubled LDS images -- the layers where it beats the tuned fp32 kernels (tools/conv_breakdown.py)
-            bf16 = (transposed and W >= 32) or (not transposed and (
-                pc.stride == 1 or (pc.stride == 2 and pc.G == 1 and OW >= 32)))
-    elif bf16 and not bf_ok:
-        raise RuntimeError("conv2d: this layer is not eligible for the bf16 kernel (see bf16_eligible)")
-    if rv and not bf16rv_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset):
-        raise RuntimeError("conv2d: this layer is not eligible for the row-vector bf16 kernel (see bf16rv_eligible)")
-    if dg and not bf16dg_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset, in_shift):
-        raise RuntimeError("conv2d: this layer is not eligible for the dilation-group bf16 kernel (see bf16dg_eligible)")
-    rv = rv or dg   # (the same activation-type requirement below)
-    if rv and not (x.dtype == BF or (ACT_BF16 and out is None)) or (rv and out is not None and out.dtype != BF):
-        raise RuntimeError("conv2d: bf16='rv' names the row-vector kernel, which reads and writes bf16 activations: pass a bf16 input "
-                           "(and output) or switch ACT_BF16 on")
-    # bf16 activations: the bf16 kernel (not its split-precision form) reads and writes bf16 when the configuration asks for it or
-    # the caller hands it a bf16 tensor; every other kernel is fp32 on both sides
-    io_bf = bool(bf16) and not x3 and (x.dtype == BF or (ACT_BF16 and out is None)) and (out is None or out.dtype == BF)
-    act_dt = BF if io_bf else torch.float32
+    # decided before anything is allocated: the family fixes the activation dtype
+    r = conv_route(pc, B, H, W, OH, OW, transposed, out_stride, out_offset, in_shift is not None, x.dtype, None if out is None else out.dtype,
+                   winograd, bf16, tile_hint, wino_form)
+    act_dt = BF if r.io_bf16 else torch.float32
     x = as_dtype(x, act_dt)
     res1, res2 = as_dtype(res1, act_dt), as_dtype(res2, act_dt)
-    if out is None and transposed:
-        out = torch.empty((B, pc.cout, 2 * H + 1, 2 * W + 1), device=x.device, dtype=act_dt)
     if out is None:
-        yh, yw = out_hw if out_hw is not None else (OH, OW)
+        yh, yw = (2 * H + 1, 2 * W + 1) if transposed else (out_hw if out_hw is not None else (OH, OW))
         out = torch.empty((B, pc.cout, yh, yw), device=x.device, dtype=act_dt)
-    _req(out, "out", bf16_ok=io_bf)
+    _req(out, "out", bf16_ok=r.io_bf16)
     if out.dtype != act_dt:
         raise RuntimeError(f"conv2d: `out` is {out.dtype} but this launch writes {act_dt}")
     if B == 0:  # empty batch: nothing to enqueue (an empty tensor has no device pointer to hand to the C ABI)
@@ -731,11 +807,11 @@ def conv2d_packed(x, pc, out=None, out_hw=None, y_coff=0, out_stride=(1, 1), out
     keep = [x, pc.w, out, _opt(in_scale, "in_scale"), _opt(in_shift, "in_shift"), _opt(out_scale, "out_scale"),
             _opt(ch_scale, "ch_scale"), _opt(ch_bias, "ch_bias"), _opt(bias1, "bias1"), _opt(noise, "noise"),
             _opt(noise_w, "noise_w"), _opt(bias2, "bias2"), _opt(prelu, "prelu"),
-            _req(res1, "res1", io_bf) if res1 is not None else None, _req(res2, "res2", io_bf) if res2 is not None else None]
+            _req(res1, "res1", r.io_bf16) if res1 is not None else None, _req(res2, "res2", r.io_bf16) if res2 is not None else None]
     dp = [(t.data_ptr() if t is not None else None) for t in keep]
     (p.x, p.w, p.y, p.in_scale, p.in_shift, p.out_scale, p.ch_scale, p.ch_bias, p.bias1, p.noise, p.noise_w, p.bias2,
      p.prelu, p.res1, p.res2) = dp
-    p.io_bf16 = 1 if io_bf else 0
+    p.io_bf16 = 1 if r.io_bf16 else 0
     p.B, p.Cin, p.H, p.W = B, Cin, H, W
     p.G, p.cout_g, p.OH, p.OW, p.KH, p.KW = pc.G, pc.cout_g, OH, OW, pc.kh, pc.kw
     p.stride_y = p.stride_x = pc.stride
@@ -750,128 +826,25 @@ def conv2d_packed(x, pc, out=None, out_hw=None, y_coff=0, out_stride=(1, 1), out
     rt = res1 if res1 is not None else res2
     p.res_ch = rt.shape[1] if rt is not None else 0
     p.res_coff = res_coff
-    if bf16:
-        winograd = False
-        if tile_hint < 0:
-            tile_hint = 0
-    wino_ok = winograd_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset)
-    named_fused = winograd == 5       # the caller asked for the fused F(4x4) kernel by name: no silent fall-back (tests, tuners)
-    if winograd is None:
-        winograd = wino_ok and tile_hint == 0 and WINO.get(key, WINO.get("8" + key[key.index(","):], False))
-    elif winograd and not wino_ok:
-        raise RuntimeError("conv2d: this layer is not eligible for the Winograd kernel (3x3, stride 1, dilation 1, pad 1, G = 1)")
-    if winograd == 4 and winograd is not True and not winograd4_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset, in_shift):
-        winograd = True     # (the deep-layer form does not serve this call's operands: F(2x2,3x3))
-    if winograd == 5 and not winograd4f_eligible(pc, H, W, OH, OW, transposed, out_stride, out_offset, in_shift):
-        if named_fused:
-            raise RuntimeError("conv2d: this launch is not eligible for the fused F(4x4,3x3) kernel (winograd4f_eligible: one group or up to four "
-                               "dilation groups over one shared input, 3x3 / stride 1 / padding = dilation in {1, 2, 4, 8}, H and W multiples of "
-                               "4 x dilation, no affine shift, Cin % 8 == 0 up to 512, W >= 16)")
-        winograd = True
-    if RECORDER is not None:
-        RECORDER.append((key, (B, Cin, H, W, OH, OW), pc, transposed))
-    p.tile_hint = tile_hint
+    p.tile_hint = r.hint
     p.x_ch, p.x_group_stride = x_ch, pc.x_group_stride
     p.transposed = 1 if transposed else 0
     p.dil_by_input_quarter = 1 if pc.dil_by_input_quarter else 0
+    if RECORDER is not None:
+        RECORDER.append((r.key, (B, Cin, H, W, OH, OW), pc, transposed))
     if rt is not None and (rt.shape[0] != B or rt.shape[2] != out.shape[2] or rt.shape[3] != out.shape[3]):
         raise RuntimeError("conv2d: residual must match the output tensor's batch and spatial size")
     prof = PROFILER
     if prof is not None:
         start = prof.begin()
-    ran_rv = False
-    if bf16 and x3:
-        bw = pc.bf16x3_weight()
-        keep.append(bw)
-        p.w = bw.data_ptr()
-        if tile_hint == 0:
-            p.tile_hint = BF16X3_TUNE.get(key, BF16X3_TUNE.get("8" + key[key.index(","):], 0))
-            if BF16_FORCE:
-                p.tile_hint = BF16_FORCE
-        rc = lib.vsp_conv2d_bf16x3(C.byref(p), _stream())
-        if rc != 0 and BF16_FORCE and tile_hint == 0:  # tuner: the forced variant does not serve this launch
-            p.tile_hint = 0
-            rc = lib.vsp_conv2d_bf16x3(C.byref(p), _stream())
-        if rc == -3:  # VSP_ENOTSUP: the doubled LDS images of this shape do not fit (small stride-2 maps) -> the fp32 kernel
-            p.w, bf16 = pc.w.data_ptr(), False
-            check(lib.vsp_conv2d_f32(C.byref(p), _stream()), "conv2d")
-        else:
-            check(rc, "conv2d_bf16x3")
-    elif bf16 and io_bf and (dg or (dg is None and BF16_DG and pc.G > 1 and tile_hint == 0 and not BF16_FORCE and rv is None)) and bf16dg_eligible(
-            pc, H, W, OH, OW, transposed, out_stride, out_offset, in_shift) and _bf16dg_call(p, pc, keep, dg):
-        ran_rv = "dg"
-    elif bf16 and not dg and (rv or (rv is None and BF16_RV and tile_hint == 0 and not BF16_FORCE)) and io_bf and bf16rv_eligible(
-            pc, H, W, OH, OW, transposed, out_stride, out_offset) and (rv or bf16rv_profitable(pc, H, W)) and _bf16rv_call(p, pc, keep, rv):
-        ran_rv = True
-    elif bf16:
-        modw = (BF16_MODW and io_bf and in_scale is not None and in_scale_per_sample and in_shift is None and pc.x_group_stride == 0
-                and W % 2 == 0 and in_scale.dim() == 2 and in_scale.shape == (B, Cin) and x.data_ptr() % 4 == 0)
-        if modw:
-            # the style goes into per-image weights (the reference's fused form): the kernel's staging becomes a copy (conv_bf16.hip NOSC)
-            bw, wbytes = bf16_modulated_weight(pc, in_scale)
-            p.in_scale, p.in_scale_bstride, p.w_bstride = None, 0, wbytes
-        else:
-            bw = pc.bf16_weight()
-        keep.append(bw)
-        p.w = bw.data_ptr()
-
-        def launch_bf16(strict=True):
-            rc = lib.vsp_conv2d_bf16(C.byref(p), _stream())
-            if rc == -3 and p.w_bstride:   # VSP_ENOTSUP: this tile's patch plane is too large for the copy-only staging -> shared weights + style scale
-                b2 = pc.bf16_weight()
-                keep.append(b2)
-                p.w, p.w_bstride, p.in_scale, p.in_scale_bstride = b2.data_ptr(), 0, in_scale.data_ptr(), Cin
-                rc = lib.vsp_conv2d_bf16(C.byref(p), _stream())
-            if strict:
-                check(rc, "conv2d_bf16")
-            return rc
-        if tile_hint == 0:
-            p.tile_hint = BF16_TUNE.get(key, BF16_TUNE.get("8" + key[key.index(","):], 0))
-            if BF16_FORCE:
-                p.tile_hint = BF16_FORCE
-                if launch_bf16(strict=False) != 0:  # the forced variant does not serve this launch
-                    p.tile_hint = 0
-                    launch_bf16()
-            else:
-                launch_bf16()
-        else:
-            launch_bf16()
-    elif winograd:
-        rc = -3
-        if winograd == 5:
-            u4 = pc.winograd4f_weight()
-            keep.append(u4)
-            p.w = u4.data_ptr()
-            rc = lib.vsp_conv2d_winograd4f_f32(C.byref(p), _stream())
-            if rc not in (0, -3) or (rc == -3 and named_fused):
-                check(rc, "conv2d_winograd4f")
-            if rc == -3:   # VSP_ENOTSUP: alignment of an operand plane -> F(2x2,3x3)
-                winograd = True
-        elif winograd == 4 and winograd is not True:
-            u4 = pc.winograd4_weight()
-            nfl = lib.vsp_conv2d_winograd4_work_floats(C.byref(p))
-            work = torch.empty(nfl, device=x.device, dtype=torch.float32)   # V = B^T d B in fragment order (2.25 x the input)
-            keep += [u4, work]
-            p.w = u4.data_ptr()
-            rc = lib.vsp_conv2d_winograd4_f32(C.byref(p), _ptr(work), nfl, _stream())
-            if rc not in (0, -3):
-                check(rc, "conv2d_winograd4")
-            if rc == -3:   # VSP_ENOTSUP: alignment of an operand plane -> F(2x2,3x3)
-                winograd = True
-        if rc == -3:
-            uw = pc.winograd_weight()
-            keep.append(uw)
-            p.w = uw.data_ptr()
-            p.tile_hint = wino_form
-            check(lib.vsp_conv2d_winograd_f32(C.byref(p), _stream()), "conv2d_winograd")
-    else:
-        check(lib.vsp_conv2d_f32(C.byref(p), _stream()), "conv2d")
+    ran = _LAUNCH[r.family](p, pc, keep, r.named, in_scale)
     if prof is not None:
-        es = 2 if io_bf else 4
+        es = 2 if r.io_bf16 else 4
         n_out_el = B * pc.cout * ((2 * H + 1) * (2 * W + 1) if transposed else OH * OW)
-        nbytes = (x.numel() + n_out_el * (1 + (res1 is not None) + (res2 is not None))) * es + pc.cout * Cin * pc.kh * pc.kw * (2 if bf16 else 4) + (
-            B * OH * OW * 4 if noise is not None else 0)
-        prof.end(start, 2.0 * B * pc.cout * (H * W if transposed else OH * OW) * Cin * pc.kh * pc.kw, (Cin, pc.cout, OH, OW, pc.kh, pc.stride, pc.G, ("bf16x3" if x3 else (("bf16dg" if ran_rv == "dg" else "bf16rv") if ran_rv else "bf16")) if bf16 else (("wino4f" if winograd == 5 else ("wino4" if (winograd == 4 and winograd is not True) else "wino")) if winograd else ("tconv" if transposed else "direct")), key), nbytes)
+        nbytes = (x.numel() + n_out_el * (1 + (res1 is not None) + (res2 is not None))) * es + pc.cout * Cin * pc.kh * pc.kw * (
+            2 if ran.startswith("bf16") else 4) + (B * OH * OW * 4 if noise is not None else 0)
+        prof.end(start, 2.0 * B * pc.cout * (H * W if transposed else OH * OW) * Cin * pc.kh * pc.kw,
+                 (Cin, pc.cout, OH, OW, pc.kh, pc.stride, pc.G, ran, r.key), nbytes)
     return out
 
 
@@ -1598,7 +1571,7 @@ def degrade_up(lq, items, n, Hh, Ww):
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types
-    skip = {"conv_key", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check"}
+    skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check"}
     g = globals()
     for name, obj in list(g.items()):
         if isinstance(obj, types.FunctionType) and not name.startswith("_") and name not in skip and obj.__module__ == __name__:
@@ -1606,3 +1579,6 @@ def _guard_public_ops():
 
 
 _guard_public_ops()
+# PackedConv.form: kernel family -> its weight layout (the device-guarded builders)
+WEIGHT_FORMS = {"wino": winograd_weight, "wino4": winograd4_weight, "wino4f": winograd4f_weight, "bf16": bf16_weight, "bf16x3": bf16x3_weight,
+                "bf16rv": bf16rv_weight, "bf16dg": bf16dg_weight}
