@@ -388,6 +388,54 @@ def test_row_helpers(H):
     close(H.demod_coefs(dev(st), dev(wsq), 0.1), torch.rsqrt(0.01 * (st ** 2) @ wsq.t() + 1e-8), 2e-5, 1e-6)
 
 
+def _row_close(got, ref64, ref32, what):
+    """max|HIP - float64| <= 4 * e_ref + 2e-6 * max|float64| with e_ref = max|torch fp32 on the CPU - float64| (the rule of
+    tests/test_tacc_kernels.py: nothing in the bound comes from the kernel)."""
+    got = got.detach().cpu().double()
+    assert got.shape == ref64.shape and torch.isfinite(got).all(), what
+    e_ref = float((ref32.double() - ref64).abs().max())
+    err = float((got - ref64).abs().max())
+    tol = 4 * e_ref + 2e-6 * float(ref64.abs().max())
+    print(f"ROW {what}: e_ref={e_ref:.3e} e_hip={err:.3e} ratio={err / e_ref if e_ref else float('nan'):.2f} tol={tol:.3e}")
+    assert err <= tol, f"{what}: max|d|={err:.3e} tol={tol:.3e} (e_ref {e_ref:.3e})"
+
+
+@pytest.mark.parametrize("rows", [1, 4, 5, 1025])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 512, 513, 1000])
+def test_row_helpers_shapes_and_ranges(H, n, rows):
+    """layernorm / softmax_lastdim over rows of length n, softmax_dim1 / pixelnorm_dim1 over a dim 1 of length n with `rows` columns
+    behind it, against float64: row lengths around the wave width and off it, row counts around the 4 rows per workgroup, softmax
+    inputs with a common offset of +100 and with a spread beyond expf's fp32 range (a lost max gives inf / nan), layernorm rows with
+    mean 1e3 and unit variance (a one-pass variance loses everything).  The TACC kernels inline the same reductions.
+    Not every printed ratio is under 4: pixelnorm_dim1 over 512 and more rows is at 4 ... 5.6 e_ref (errors of 1 ... 3.5e-6 on values of
+    |max| ~5) and passes through the additive 2e-6 * max|ref| term -- its thread sums the squares serially with fmaf, torch pairwise."""
+    g = torch.Generator().manual_seed(n * 10000 + rows)
+
+    def draw(*shape):
+        return torch.randn(*shape, generator=g, dtype=torch.float64)
+
+    for tag, x in (("n01", draw(rows, n)), ("offset", draw(rows, n) + 100.0), ("spread", draw(rows, n) * 60.0)):
+        x = x.float()
+        if tag == "spread" and n >= 63:
+            assert float(x.max() - x.min()) > 100
+        _row_close(H.softmax_lastdim(dev(x)), torch.softmax(x.double(), -1), torch.softmax(x, -1), f"softmax_lastdim {tag} {rows}x{n}")
+        x3 = x.t().contiguous().view(1, n, rows)
+        _row_close(H.softmax_dim1(dev(x3)), torch.softmax(x3.double(), 1), torch.softmax(x3, 1), f"softmax_dim1 {tag} 1x{n}x{rows}")
+    x = draw(2, n, rows).float() * 3
+    _row_close(H.softmax_dim1(dev(x)), torch.softmax(x.double(), 1), torch.softmax(x, 1), f"softmax_dim1 2x{n}x{rows}")
+    _row_close(H.pixelnorm_dim1(dev(x)), O.pixel_norm(x.double()), O.pixel_norm(x), f"pixelnorm_dim1 2x{n}x{rows}")
+    for tag, x in (("n01", draw(rows, n)), ("mean1e3", draw(rows, n) + 1e3)):
+        x = x.float()
+        a = draw(rows, n).float()
+        gm, bt = (torch.rand(n, generator=g, dtype=torch.float64) + 0.5).float(), draw(n).float()
+        _row_close(H.layernorm(dev(x)), F.layer_norm(x.double(), (n,)), F.layer_norm(x, (n,)), f"layernorm {tag} {rows}x{n}")
+        _row_close(H.layernorm(dev(x), add=dev(a)), F.layer_norm(x.double() + a.double(), (n,)), F.layer_norm(x + a, (n,)),
+                   f"layernorm add {tag} {rows}x{n}")
+        _row_close(H.layernorm(dev(x), gamma=dev(gm), beta=dev(bt), post_lrelu=True),
+                   F.leaky_relu(F.layer_norm(x.double(), (n,), gm.double(), bt.double()), 0.2) * math.sqrt(2),
+                   F.leaky_relu(F.layer_norm(x, (n,), gm, bt), 0.2) * math.sqrt(2), f"layernorm affine {tag} {rows}x{n}")
+
+
 def test_linear_many_rows_is_row_independent(H):
     """The small-GEMM kernel's wide form (M >= 1024: four row blocks per workgroup share the B fragments): against float64, and
     BIT-identical to the same rows computed in slices that take the one-block form (an image's result must not depend on the batch)."""

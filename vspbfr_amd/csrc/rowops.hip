@@ -49,18 +49,21 @@ __global__ __launch_bounds__(256) void layernorm_kernel(float* out, const float*
   if (row >= rows) return;
   const float* xr = x + (int64_t)row * cols;
   const float* ar = add ? add + (int64_t)row * cols : nullptr;
+  // Sums run on x - pivot (the row's first element): with a large common part (rows of mean 1e3 and unit variance) the fp32 sum of the
+  // raw values, and the mean rounded at the magnitude of that common part, would cost the result 1e-4; the differences are small.
+  const float pivot = xr[0] + (ar ? ar[0] : 0.f);
   float s = 0.f;
-  for (int c = lane; c < cols; c += 64) s += xr[c] + (ar ? ar[c] : 0.f);
-  const float mean = wave_sum(s) / (float)cols;
+  for (int c = lane; c < cols; c += 64) s += (xr[c] + (ar ? ar[c] : 0.f)) - pivot;
+  const float mean = wave_sum(s) / (float)cols;   // of x - pivot
   float q = 0.f;
   for (int c = lane; c < cols; c += 64) {
-    const float d = xr[c] + (ar ? ar[c] : 0.f) - mean;
+    const float d = (xr[c] + (ar ? ar[c] : 0.f)) - pivot - mean;
     q = fmaf(d, d, q);
   }
   const float inv = rsqrtf(wave_sum(q) / (float)cols + eps);
   float* orow = out + (int64_t)row * cols;
   for (int c = lane; c < cols; c += 64) {
-    float v = (xr[c] + (ar ? ar[c] : 0.f) - mean) * inv;
+    float v = ((xr[c] + (ar ? ar[c] : 0.f)) - pivot - mean) * inv;
     if (gamma) v = v * gamma[c] + (beta ? beta[c] : 0.f);
     if (post == 1) v = (v > 0.f ? v : v * slope) * gain;
     orow[c] = v;

@@ -1318,7 +1318,21 @@ def tacc_chain(x, blocks, steps, coef_idx=None, c1=None, c2=None, t_div=1.0, hea
     work = torch.empty(nfl, device=x.device, dtype=torch.float32)
     steps = [int(s) for s in steps]
     st = (C.c_int * len(steps))(*steps)
+    # the C entry checks step[s] as it reaches it, after the earlier steps have been enqueued on x: every step is checked here first, so
+    # that a refused call has launched nothing
+    for t in (steps if B and n else ()):
+        if not 0 <= t < int(head_steps):
+            raise RuntimeError(f"tacc_chain: step {t} outside the prepared heads [0, {int(head_steps)})")
+    if coef_idx is not None and len(coef_idx) != len(steps):
+        raise RuntimeError(f"tacc_chain: coef_idx has {len(coef_idx)} entries for {len(steps)} steps")
     ci = (C.c_int * len(steps))(*[int(k) for k in coef_idx]) if coef_idx is not None else None
+    if c1 is not None and c2 is not None:
+        # the C entry range-checks `step` against the prepared heads but has no length for the coefficient tables: the kernels read
+        # c1[k] / c2[k] wherever k points, so the tables' own length is checked here
+        ntab = min(c1.numel(), c2.numel())
+        for k in (steps if coef_idx is None else [int(k) for k in coef_idx]):
+            if not 0 <= k < ntab:
+                raise RuntimeError(f"tacc_chain: coefficient index {k} outside the c1 / c2 tables [0, {ntab})")
     p = TaccChainParams()
     p.B, p.n_tok, p.dim, p.n_blocks = B, 18, 512, n
     p.blocks = arr
