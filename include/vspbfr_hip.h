@@ -406,6 +406,27 @@ int vsp_subsample_f32(float* out, const float* x, int64_t planes, int IH, int IW
  *   t = (clamp(x, lo, hi) - lo) / max(hi - lo, 1e-5);  out[b,y,x,c] = (uint8) clamp(t * 255 + 0.5, 0, 255) */
 int vsp_quantize_u8_nhwc(uint8_t* out, const float* x, int B, int C, int H, int W, float lo, float hi,
                          vsp_stream_t stream);
+/* Pair statistics of two 8-bit images a, b of shape (B, H, W, C), dense, C = 1 or 3 -- the bytes a PNG writer puts on disk
+ * (vsp_quantize_u8_nhwc) -- from which PSNR and SSIM of every image pair follow:
+ *   sse[i]  = sum over pixels and channels of (a - b)^2, exact.  PSNR = 10 log10(255^2 H W C / sse[i]), formed by the
+ *             caller in float64 (the reference's my_lpips.psnr(p0, p1, 255.), my_lpips/__init__.py:57-58).
+ *   ssim[i] = mean over channels and over the VALID window positions ((H - w + 1) x (W - w + 1): scikit-image's crop by
+ *             (w - 1) / 2) of ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = (0.01 * 255)^2,
+ *             C2 = (0.03 * 255)^2, with the window
+ *     VSP_WIN_UNIFORM7: 7 x 7 box, sample covariance (x 49 / 48): scikit-image's structural_similarity defaults, i.e. what
+ *                       the reference's my_lpips.dssim(p0, p1, range=255.) measures (dssim = (1 - ssim) / 2, :60-61);
+ *     VSP_WIN_GAUSS11:  11 x 11 separable Gaussian, sigma 1.5, taps normalised to sum 1, population covariance (Wang et al.
+ *                       2004; scikit-image with gaussian_weights=True, use_sample_covariance=False).
+ * Box-window moments are exact 32-bit integers up to one fp32 ratio per position; Gaussian moments are fp32 around the
+ * tile's mean; positions are added in float64 in a fixed order.  Image i gets the same bits for every B and on every launch.
+ * `work`: vsp_pair_stats_work_bytes(B, H, W, C, window) bytes of device memory, 8-byte aligned, private to the call until
+ * it has finished on `stream` (0 is returned for arguments vsp_pair_stats_u8 refuses).
+ * VSP_EINVAL: H or W below the window, C not 1 or 3, unknown window, null pointer, B > 65535, H or W > 32768. */
+#define VSP_WIN_UNIFORM7 7
+#define VSP_WIN_GAUSS11 11
+size_t vsp_pair_stats_work_bytes(int B, int H, int W, int C, int window);
+int vsp_pair_stats_u8(unsigned long long* sse, double* ssim, const uint8_t* a, const uint8_t* b, int B, int H, int W, int C,
+                      int window, void* work, vsp_stream_t stream);
 /* F.interpolate(x, (OH, OW), mode="bilinear", align_corners=False) on `planes` = B*C planes (the resize to 256^2 in front of the
  * e4e encoder, reference Loss/e4e_embedding.py:91-100, for inputs that are not 512^2 -- there it is the 2x2 mean above). */
 int vsp_resize_bilinear_f32(float* out, const float* x, int64_t planes, int IH, int IW, int OH, int OW, vsp_stream_t stream);

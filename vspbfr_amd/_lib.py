@@ -105,6 +105,7 @@ class DegradeItem(C.Structure):
 
 DEGRADE_HAZE, DEGRADE_GREY = 1, 2            # vsp_degrade_item.flags (include/vspbfr_hip.h VSP_DEGRADE_*)
 DEGRADE_MAX_KSIZE, DEGRADE_MAX_SIZE, DEGRADE_MAX_ITEMS = 41, 2048, 1024
+WIN_UNIFORM7, WIN_GAUSS11 = 7, 11            # vsp_pair_stats_u8 window (include/vspbfr_hip.h VSP_WIN_*)
 
 _i, _i64, _f, _p = C.c_int, C.c_int64, C.c_float, C.c_void_p
 
@@ -185,11 +186,13 @@ SIGNATURES = {
     "vsp_degrade_down_u8": [_p, _p, _p, _p, _p, _i, _i, _i, _i, C.c_uint64, _i64, _p],
     "vsp_degrade_jpeg_u8": [_p, _p, _p, _i, _i, _i, _p],
     "vsp_degrade_up_f32": [_p, _p, _p, _i, _i, _i, _p],
+    "vsp_pair_stats_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
           "vsp_winograd_weight_floats": [_i, _i, _i], "vsp_winograd4_weight_floats": [_i, _i], "vsp_winograd4f_weight_floats": [_i, _i],
-          "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i]}
+          "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i],
+          "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i]}
 
 
 def _load():

@@ -1356,6 +1356,43 @@ def quantize_u8_nhwc(x, lo=-1.0, hi=1.0):
     return out
 
 
+PAIR_WINDOWS = {"uniform7": 7, "gauss11": 11}      # include/vspbfr_hip.h VSP_WIN_UNIFORM7 / VSP_WIN_GAUSS11
+
+
+def _req_u8(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name} must be a tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA tensor")
+    if t.dtype != torch.uint8:
+        raise RuntimeError(f"{name} must be uint8 (got {t.dtype})")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+    return t
+
+
+def pair_stats_u8(a, b, window="gauss11"):
+    """a, b: (B, H, W, C) uint8 on one device, C = 1 or 3 -> (sse int64 (B,), ssim float64 (B,)) on that device, on the current
+    stream, without synchronising (vsp_pair_stats_u8: exact sum of squared differences; mean SSIM over the valid positions of the
+    `uniform7` or `gauss11` window).  The workspace (16 bytes per 32 x 32 tile) comes from torch's caching allocator per call, which
+    reuses the block on the stream that used it: calls on different streams never share partial sums."""
+    a, b = _req_u8(a, "a"), _req_u8(b, "b")
+    if a.device != b.device:
+        raise RuntimeError(f"operands on different devices: {a.device} and {b.device}")
+    if a.dim() != 4 or a.shape != b.shape:
+        raise RuntimeError(f"pair_stats_u8: a and b must be (B, H, W, C) of one shape (got {tuple(a.shape)} and {tuple(b.shape)})")
+    if window not in PAIR_WINDOWS:
+        raise RuntimeError(f"pair_stats_u8: window must be one of {sorted(PAIR_WINDOWS)} (got {window!r})")
+    win = PAIR_WINDOWS[window]
+    B, Hh, Ww, Cc = (int(v) for v in a.shape)
+    sse = torch.empty(B, device=a.device, dtype=torch.int64)
+    ssim = torch.empty(B, device=a.device, dtype=torch.float64)
+    work = torch.empty(max(int(lib.vsp_pair_stats_work_bytes(B, Hh, Ww, Cc, win)) // 8, 1), device=a.device, dtype=torch.float64)
+    check(lib.vsp_pair_stats_u8(C.c_void_p(sse.data_ptr()), C.c_void_p(ssim.data_ptr()), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                B, Hh, Ww, Cc, win, C.c_void_p(work.data_ptr()), _stream()), "pair_stats_u8")
+    return sse, ssim
+
+
 # ----------------------------------------------------------------------------------------------- keyed random tensors
 # segment ids of the path's draws (they enter the Philox counter: a tensor keeps its values whatever else is drawn with it)
 SEG_LQ, SEG_XT, SEG_Z = 1, 2, 3           # synthetic LQ batch (bench), x_T (ldm/ddpm.py:423), z (restoration_test.py:77-82; +1: second mixing code)

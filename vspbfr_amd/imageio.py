@@ -97,14 +97,17 @@ class PngWriter:
         self.pending = []
 
     def submit(self, batch, paths):
-        """batch: (B, 3, H, W) fp32 on the device in [-1, 1] (values outside are clamped like save_image does)."""
+        """batch: (B, 3, H, W) fp32 on the device in [-1, 1] (values outside are clamped like save_image does), or the
+        (B, H, W, 3) uint8 tensor such a batch quantises to.  Returns the uint8 device tensor whose bytes go to disk (what
+        vspbfr_amd.metrics scores)."""
         from . import hip_ops as H
-        u8 = H.quantize_u8_nhwc(batch.contiguous(), -1.0, 1.0)
+        u8 = batch if batch.dtype == torch.uint8 else H.quantize_u8_nhwc(batch.contiguous(), -1.0, 1.0)
         host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(u8, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self.pending.append(self.pool.submit(self._encode, host, ev, list(paths)))
+        return u8
 
     @staticmethod
     def _encode(host, ev, paths):

@@ -1,0 +1,185 @@
+"""Full-reference image quality of restored faces against ground truth, measured on the device: PSNR, SSIM and -- with
+user-supplied weights -- LPIPS and identity similarity.
+
+The reference has the pixel metrics as host code for one image at a time (my_lpips.psnr / my_lpips.dssim,
+my_lpips/__init__.py:57-61; networks_basic.DSSIM / L2, networks_basic.py:143-180) and never calls them.  Here they come from
+one kernel launch per batch (`hip_ops.pair_stats_u8`: exact sum of squared differences + mean SSIM over the valid window
+positions) on the SAME uint8 tensors the PNG writer sends to disk, so a reported number is the number anyone gets from the
+files.  Nothing below synchronises with the host until `Evaluator.report()`.
+
+Windows: "gauss11" (11 x 11 Gaussian, sigma 1.5, population covariance: Wang et al. 2004, the form restoration papers report)
+and "uniform7" (7 x 7 box, sample covariance: scikit-image's defaults, what the reference's `dssim` computes)."""
+import json
+import math
+
+import torch
+
+WINDOWS = ("gauss11", "uniform7")
+PEAK = 255.0
+
+
+def psnr_from_sse(sse, count):
+    """PSNR of an 8-bit image pair from its exact sum of squared differences over `count` samples, in float64 on the host
+    (the reference's psnr(p0, p1, 255.): 10 log10(peak^2 / mse)); None when the images are identical."""
+    sse, count = int(sse), int(count)
+    if sse == 0:
+        return None
+    return 10.0 * math.log10(PEAK * PEAK * count / sse)
+
+
+def _as_u8_pair(a, b):
+    from . import hip_ops as H
+    if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor)):
+        raise RuntimeError("metrics: operands must be tensors")
+    if a.dtype != b.dtype or a.shape != b.shape:
+        raise RuntimeError(f"metrics: operands differ in dtype or shape ({a.dtype} {tuple(a.shape)} vs {b.dtype} {tuple(b.shape)})")
+    if a.dtype == torch.uint8:
+        if a.dim() != 4 or a.shape[3] != 3:
+            raise RuntimeError(f"metrics: uint8 operands must be (B, H, W, 3) (got {tuple(a.shape)})")
+        return a, b
+    if a.dtype == torch.float32:
+        if a.dim() != 4 or a.shape[1] != 3:
+            raise RuntimeError(f"metrics: float operands must be (B, 3, H, W) in [-1, 1] (got {tuple(a.shape)})")
+        return H.quantize_u8_nhwc(a.contiguous(), -1.0, 1.0), H.quantize_u8_nhwc(b.contiguous(), -1.0, 1.0)
+    raise RuntimeError(f"metrics: operands must be float32 (B, 3, H, W) or uint8 (B, H, W, 3) (got {a.dtype})")
+
+
+def psnr_ssim(a, b, window="gauss11"):
+    """Two (B, 3, H, W) float32 tensors in [-1, 1] (quantised to 8 bits the way the PNG writer does) or two (B, H, W, 3) uint8
+    tensors -> (psnr float64 (B,), ssim float64 (B,)) on the device; psnr is +inf for identical images.  No synchronisation."""
+    from . import hip_ops as H
+    a, b = _as_u8_pair(a, b)
+    sse, ssim = H.pair_stats_u8(a, b, window)
+    count = float(a.shape[1] * a.shape[2] * a.shape[3])
+    psnr = 10.0 * torch.log10((PEAK * PEAK * count) / sse.to(torch.float64))
+    return psnr, ssim
+
+
+def dequantize(u8):
+    """(B, H, W, 3) uint8 -> (B, 3, H, W) float32 in [-1, 1]: the image a reader of the PNG file gets (u8 / 127.5 - 1)."""
+    return (u8.permute(0, 3, 1, 2).to(torch.float32) / 127.5 - 1.0).contiguous()
+
+
+def _mean(values):
+    values = [v for v in values if v is not None]
+    return math.fsum(values) / len(values) if values else None
+
+
+def summarize(rows, dataset=None, window="gauss11"):
+    """The report of a list of per-image rows: mean of every column present (mean PSNR = mean of the per-image PSNR over the
+    pairs that have one; identical pairs are counted in `psnr_infinite`)."""
+    rows = sorted(rows, key=lambda r: r["index"])
+    cols = [c for c in ("psnr", "ssim", "lpips", "id") if any(c in r for r in rows)]
+    return {
+        "dataset": dataset, "count": len(rows), "window": window,
+        "psnr_infinite": sum(1 for r in rows if r.get("psnr") is None),
+        "mean": {c: _mean([r.get(c) for r in rows]) for c in cols},
+        "images": rows,
+    }
+
+
+class Evaluator:
+    """Scores batches of restored images against their ground truth.
+
+        ev = Evaluator(window="gauss11", lpips=PerceptualLoss(...) or None, idloss=IDLoss(...) or None)
+        ev.add(restored_u8, gt_u8, names)      # per batch, (B, H, W, 3) uint8 on the device; no host synchronisation
+        report = ev.report(dataset="celeba")   # one device-to-host copy of all columns: the only synchronisation
+
+    `names`: one `(lq, hq)` pair of file names per image (or None).  `lpips` / `idloss` add the columns `lpips`
+    (= PerceptualLoss(restored, gt) per image) and `id` (= cosine of the IDLoss.get_id embeddings per image); both see the
+    de-quantised uint8 images, so every column describes the files on disk."""
+
+    def __init__(self, window="gauss11", lpips=None, idloss=None):
+        if window not in WINDOWS:
+            raise ValueError(f"window must be one of {WINDOWS} (got {window!r})")
+        self.window, self.lpips, self.idloss = window, lpips, idloss
+        self.meta = []       # (index, lq, hq, samples per image)
+        self.dev = {"sse": [], "ssim": [], "lpips": [], "id": []}
+
+    def __len__(self):
+        return len(self.meta)
+
+    def add(self, restored, gt, names=None, indices=None):
+        from . import hip_ops as H
+        if restored.dtype != torch.uint8 or gt.dtype != torch.uint8:
+            raise RuntimeError("Evaluator.add takes the (B, H, W, 3) uint8 tensors that go to disk (hip_ops.quantize_u8_nhwc)")
+        restored, gt = _as_u8_pair(restored, gt)
+        B = restored.shape[0]
+        names = [(None, None)] * B if names is None else [tuple(n) for n in names]
+        indices = list(range(len(self.meta), len(self.meta) + B)) if indices is None else [int(i) for i in indices]
+        if len(names) != B or len(indices) != B or any(len(n) != 2 for n in names):
+            raise RuntimeError(f"Evaluator.add: {B} images need {B} (lq, hq) name pairs and indices")
+        sse, ssim = H.pair_stats_u8(restored, gt, self.window)
+        self.dev["sse"].append(sse)
+        self.dev["ssim"].append(ssim)
+        if self.lpips is not None or self.idloss is not None:
+            with torch.no_grad():
+                r, g = dequantize(restored), dequantize(gt)
+                if self.lpips is not None:
+                    self.dev["lpips"].append(self.lpips(r, g).reshape(B).to(torch.float64))
+                if self.idloss is not None:
+                    z = self.idloss.get_id(torch.cat([r, g], 0))
+                    self.dev["id"].append((z[:B] * z[B:]).sum(1).to(torch.float64))
+        count = restored.shape[1] * restored.shape[2] * restored.shape[3]
+        self.meta.extend((i, n[0], n[1], count) for i, n in zip(indices, names))
+
+    def report(self, dataset=None):
+        cols = [k for k, v in self.dev.items() if v]
+        # one copy, one synchronisation: every column as float64 (an sse is an integer below 2^53, so it survives exactly)
+        table = torch.stack([torch.cat(self.dev[k]).to(torch.float64) for k in cols]).cpu().tolist() if self.meta else []
+        host = dict(zip(cols, table))
+        rows = []
+        for k, (index, lq, hq, count) in enumerate(self.meta):
+            sse = int(host["sse"][k])
+            row = {"index": index, "lq": lq, "hq": hq, "sse": sse, "psnr": psnr_from_sse(sse, count), "ssim": host["ssim"][k]}
+            for col in ("lpips", "id"):
+                if col in host:
+                    row[col] = host[col][k]
+            rows.append(row)
+        return summarize(rows, dataset, self.window)
+
+
+def write_report(report, path):
+    with open(path, "w") as f:
+        json.dump(report, f, indent=1, allow_nan=False)
+        f.write("\n")
+
+
+def merge_reports(paths):
+    """Join the per-rank files of one dataset (pure host code): rows by index, means recomputed over all of them."""
+    reports = []
+    for p in paths:
+        with open(p) as f:
+            reports.append(json.load(f))
+    if not reports:
+        raise ValueError("merge_reports: no files")
+    for key in ("dataset", "window"):
+        if len({r[key] for r in reports}) != 1:
+            raise ValueError(f"merge_reports: the files disagree on {key!r}: {sorted(str(r[key]) for r in reports)}")
+    rows = [row for r in reports for row in r["images"]]
+    if len({row["index"] for row in rows}) != len(rows):
+        raise ValueError("merge_reports: an image index appears more than once")
+    return summarize(rows, reports[0]["dataset"], reports[0]["window"])
+
+
+def summary_line(report):
+    m = report["mean"]
+    parts = [f"{c} {m[c]:.6g}" if m.get(c) is not None else f"{c} n/a" for c in ("psnr", "ssim", "lpips", "id") if c in m]
+    return "metrics %s (%s, %d images, %d identical): %s" % (report["dataset"], report["window"], report["count"],
+                                                            report["psnr_infinite"], ", ".join(parts))
+
+
+def load_scorers(lpips_weights=None, id_weights=None, device="cuda"):
+    """The optional learned metrics from user-supplied weight files: `lpips_weights` = "LIN[,VGG]" (the reference's
+    my_lpips/weights/v0.1/vgg.pth and a torchvision vgg16 state dict), `id_weights` = a resnet101(num_classes=256) state dict."""
+    lp = idl = None
+    if lpips_weights:
+        from .lpips import PerceptualLoss
+        parts = str(lpips_weights).split(",")
+        if len(parts) > 2 or not all(parts):
+            raise ValueError("--lpips_weights takes LIN or LIN,VGG")
+        lp = PerceptualLoss(lin_weights=parts[0], vgg_weights=parts[1] if len(parts) == 2 else None).to(device)
+    if id_weights:
+        from .id_loss import IDLoss
+        idl = IDLoss(str(id_weights), device=device)
+    return lp, idl

@@ -1,0 +1,130 @@
+"""The inference CLI with its output scored against ground truth on the device.
+
+    python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
+        --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
+
+`vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
+puts it under this repository's rule that a feature leaves every existing `*_test.py` / `test_*.py` file as it is.  This module
+is that CLI again -- same flags, same defaults, same loop, same output names (`get_store_data` is shared, the rest restated) --
+with the scoring in the loop: `PngWriter.submit` returns the uint8 device tensor whose bytes go to disk, the `restore` and `gt`
+tensors of a batch go to `metrics.Evaluator.add` (quantised once, used twice; no host synchronisation per batch, so PNG encoding
+still overlaps the next batch), and after `writer.drain()` the dataset's `metrics_<rank>.json` is written beside its PNGs and one
+summary line printed.  `--metrics` is off by default: without it the output directory is byte for byte that of
+`vspbfr_amd.restoration_test` (tests/test_metrics_cli_gpu.py compares the two).  `--metrics` with a dataset whose
+`--hq_data_list` entry is `None` is refused before anything is loaded.  Multi-GPU as restoration_test; `metrics.merge_reports`
+joins the per-rank files."""
+import argparse
+import os
+
+import torch
+
+from .e4e import E4e_embedding
+from .imageio import PngWriter, RestoreTestSet, output_name
+from .pipeline import RestorationPipeline, load_ddpm, shard_range
+from .restoration_test import get_store_data
+from .restorenet import Restoration_net
+
+
+def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, device, rank=0, world=1):
+    data = RestoreTestSet(lq_root, None if hq_root == "None" else hq_root, (args.size, args.size))
+    lo, hi = shard_range(len(data), rank, world)
+    os.makedirs(eval_dict, exist_ok=True)
+    writer = PngWriter()
+    evaluator = None
+    if args.metrics:
+        from .metrics import Evaluator
+        evaluator = Evaluator(args.ssim_window, *args.scorers)
+    print("testing!!! len:%d (rank %d handles %d..%d)" % (len(data), rank, lo, hi))
+    with torch.no_grad():
+        for start in range(lo, hi, args.batch):
+            idx = list(range(start, min(start + args.batch, hi)))
+            if args.debug and (start - lo) // args.batch > 10:
+                break
+            items = [data[i] for i in idx]
+            gts = None
+            if data.hq is not None:
+                gts = torch.stack([it[1] for it in items])
+                items = [it[0] for it in items]
+            low = torch.stack(items).to(device, non_blocking=True)
+            out = pipe(low)
+            u8 = {}
+            for kind, t in (("restore", out["restored"]), ("low", low), ("sample", out["style_sample"]), ("gt", gts)):
+                if t is not None:
+                    u8[kind] = writer.submit(t.to(device) if kind == "gt" else t, [output_name(eval_dict, i, rank, data_name, kind) for i in idx])
+            if evaluator is not None:   # the bytes that go to disk, scored on the device: no host synchronisation here
+                evaluator.add(u8["restore"], u8["gt"], [(os.path.relpath(data.lq[i], lq_root), os.path.relpath(data.hq[i], hq_root)) for i in idx], idx)
+    writer.drain()
+    if evaluator is not None:
+        from .metrics import summary_line, write_report
+        report = evaluator.report(data_name)
+        write_report(report, os.path.join(eval_dict, "metrics_%d.json" % rank))
+        print(summary_line(report))
+    return eval_dict
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Visual Style prompt restoration test with scoring against ground truth (MI355X path)")
+    ap.add_argument("--batch", type=int, default=1, help="batch sizes for each gpu")
+    ap.add_argument("--size", type=int, default=512, help="image sizes for the models")
+    ap.add_argument("--mixing", type=float, default=0.5, help="probability of latent code mixing")
+    ap.add_argument("--channel_multiplier", type=int, default=2)
+    ap.add_argument("--debug", type=bool, default=False, help="for debugging")
+    ap.add_argument("--ckpt", type=str, default=None)
+    ap.add_argument("--ddpm_ckpt", type=str, default="pre-train/code_diffuser.pt")
+    ap.add_argument("--psp_checkpoint_path", type=str, default="pre-train/style_encoder_decoder.pt")
+    ap.add_argument("--eval_dir", type=str, default="./eval_dir")
+    ap.add_argument("--lq_data_list", type=str, default="")
+    ap.add_argument("--hq_data_list", type=str, default="")
+    ap.add_argument("--data_name_list", type=str, default="")
+    ap.add_argument("--timesteps", type=int, default=4, help="extension: DDPM steps (the reference hard-codes 4, :35-38)")
+    ap.add_argument("--no_sample", action="store_true", help="extension: skip the 1024^2 tail and the *_sample.png output")
+    ap.add_argument("--conv_dtype", choices=["f32", "bf16", "bf16x3"], default="f32",
+                    help="extension: bf16 = the bf16-kernel configuration (vsp_conv2d_bf16; not the parity path); "
+                         "bf16x3 = split-precision operands on the bf16 pipe (fp32-grade)")
+    ap.add_argument("--metrics", action="store_true",
+                    help="extension: score *_restore.png against *_gt.png on the device (PSNR, SSIM; LPIPS / ID with the weights "
+                         "below) and write metrics_<rank>.json beside the PNGs; needs a ground-truth root for every dataset")
+    ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11",
+                    help="extension: SSIM window (gauss11: Wang et al.; uniform7: scikit-image's default, the reference's dssim)")
+    ap.add_argument("--lpips_weights", type=str, default=None, help="extension: LIN[,VGG] weight files; adds the lpips column")
+    ap.add_argument("--id_weights", type=str, default=None, help="extension: resnet101(256) state dict; adds the id column")
+    args = ap.parse_args(argv)
+    if not args.metrics and (args.lpips_weights or args.id_weights):
+        ap.error("--lpips_weights / --id_weights only have a meaning with --metrics")
+    if args.metrics:
+        missing = [d["name"] for d in get_store_data(args.lq_data_list, args.hq_data_list, args.data_name_list) if d["hq"] in ("None", "")]
+        if missing:
+            ap.error("--metrics needs a ground-truth root (--hq_data_list) for every dataset; none given for: " + ", ".join(missing))
+    args.latent, args.n_mlp = 512, 8
+    from . import hip_ops
+    hip_ops.BF16_CONV = {"f32": False, "bf16": True, "bf16x3": "x3"}[args.conv_dtype]
+
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+
+    g_ema = Restoration_net(args.size, args.latent, args.n_mlp, channel_multiplier=args.channel_multiplier)
+    if args.ckpt is not None:
+        print("load models:", args.ckpt)
+        try:
+            g_ema.load_state_dict(torch.load(args.ckpt, map_location="cpu")["g_ema"])
+        except RuntimeError as e:  # the reference prints and carries on with the initial weights (:246-250)
+            print(str(e))
+    g_ema = g_ema.to(device).eval()
+    name_ = os.path.basename(str(args.ckpt)).strip().split(".")[0]
+    eval_root = os.path.join(args.eval_dir, name_)
+    psp = E4e_embedding(args.psp_checkpoint_path, out_size=args.size, size=1024, device=device, use_generator=True)
+    store = get_store_data(args.lq_data_list, args.hq_data_list, args.data_name_list)
+    if args.metrics:
+        from .metrics import load_scorers
+        args.scorers = load_scorers(args.lpips_weights, args.id_weights, device)
+    for k, d in enumerate(store):
+        diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
+        pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)
+        eval_dict = os.path.join(eval_root, str(len(store) - 1), d["name"])  # the reference's `str(i)` is the last index (:174)
+        tester_restore_ddpm(args, pipe, d["lq"], d["hq"], eval_dict, d["name"], device, rank, world)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,103 @@
+"""Score two existing folders of PNGs with the device metrics of vspbfr_amd.metrics (same kernel, same report as
+`python -m vspbfr_amd.restoration_metrics`): what someone comparing against another method's outputs needs.
+
+    python -m vspbfr_amd.score --restored eval_dir/.../demo --gt eval_dir/.../demo [--pattern _restore.png/_gt.png]
+        [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--batch 8] [--out metrics.json]
+
+Pairing: a file `<stem><restored suffix>` of --restored goes with `<stem><gt suffix>` of --gt (the CLI's own naming,
+`{index}_{rank}_{name}_restore.png` / `..._gt.png`); when no file of --restored carries the suffix, the two folders are
+paired by sorted order and must hold the same number of images."""
+import argparse
+import json
+import os
+
+from .imageio import list_images
+
+
+def pair_files(restored_dir, gt_dir, pattern="_restore.png/_gt.png"):
+    """[(restored path, gt path)] -- pure host code."""
+    if pattern.count("/") != 1 or not all(pattern.split("/")):
+        raise ValueError(f"--pattern takes RESTORED_SUFFIX/GT_SUFFIX (got {pattern!r})")
+    rs, gs = pattern.split("/")
+    restored = [p for p in list_images(restored_dir) if p.endswith(rs)]
+    if restored:
+        pairs = []
+        for p in restored:
+            q = os.path.join(gt_dir, os.path.relpath(p, restored_dir)[:-len(rs)] + gs)
+            if not os.path.exists(q):
+                raise FileNotFoundError(f"no ground truth {q} for {p}")
+            pairs.append((p, q))
+        return pairs
+    a, b = list_images(restored_dir), list_images(gt_dir)
+    if os.path.abspath(restored_dir) == os.path.abspath(gt_dir):
+        raise ValueError(f"no file in {restored_dir} ends with {rs!r} and --restored and --gt are the same folder")
+    if len(a) != len(b) or not a:
+        raise ValueError(f"cannot pair by sorted order: {len(a)} images in {restored_dir}, {len(b)} in {gt_dir}")
+    return list(zip(a, b))
+
+
+def _load_u8(path):
+    import numpy as np
+    import torch
+    from PIL import Image
+    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy())
+
+
+def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda"):
+    """The report of a list of (restored, gt) files; images of one size are batched, an odd one goes alone."""
+    import torch
+
+    from .metrics import Evaluator
+    ev = Evaluator(window, lpips, idloss)
+    pend, shape = [], None
+
+    def flush():
+        if pend:
+            r = torch.stack([p[1] for p in pend]).to(device, non_blocking=True)
+            g = torch.stack([p[2] for p in pend]).to(device, non_blocking=True)
+            ev.add(r, g, [p[3] for p in pend], [p[0] for p in pend])
+            pend.clear()
+
+    for i, (rp, gp) in enumerate(pairs):
+        r, g = _load_u8(rp), _load_u8(gp)
+        if r.shape != g.shape:
+            raise ValueError(f"{rp} is {tuple(r.shape[:2])}, {gp} is {tuple(g.shape[:2])}: a pair must have one size")
+        if shape != r.shape or len(pend) >= batch:
+            flush()
+            shape = r.shape
+        pend.append((i, r, g, (os.path.basename(rp), os.path.basename(gp))))
+    flush()
+    return ev.report(dataset)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="PSNR / SSIM / LPIPS / ID of a folder of restored PNGs against ground truth (MI355X)")
+    ap.add_argument("--restored", required=True)
+    ap.add_argument("--gt", required=True)
+    ap.add_argument("--pattern", default="_restore.png/_gt.png", help="RESTORED_SUFFIX/GT_SUFFIX")
+    ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11")
+    ap.add_argument("--lpips_weights", default=None, help="LIN[,VGG] weight files; adds the lpips column")
+    ap.add_argument("--id_weights", default=None, help="resnet101(256) state dict; adds the id column")
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--dataset", default=None, help="name written into the report")
+    ap.add_argument("--out", default=None, help="write the JSON report here (default: print it)")
+    args = ap.parse_args(argv)
+    if args.batch < 1:
+        ap.error("--batch must be at least 1")
+    try:
+        pairs = pair_files(args.restored, args.gt, args.pattern)
+    except (ValueError, FileNotFoundError) as e:
+        ap.error(str(e))
+    from .metrics import load_scorers, summary_line, write_report
+    lp, idl = load_scorers(args.lpips_weights, args.id_weights)
+    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset)
+    if args.out:
+        write_report(report, args.out)
+    else:
+        print(json.dumps(report, indent=1, allow_nan=False))
+    print(summary_line(report))
+    return report
+
+
+if __name__ == "__main__":
+    main()
