@@ -40,7 +40,7 @@ const char* vsp_last_error(void);
 /* number of HIP devices visible, or a negative VSP_E* code (used by the loader's self-check). */
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
- * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item): lets a binding in
+ * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -712,6 +712,53 @@ int vsp_degrade_jpeg_u8(uint8_t* lq, uint8_t* work, const vsp_degrade_item* item
 /* up: out[i] = np.clip(round(cv2.resize(lq_i / 255, (W, H), INTER_LINEAR) * 255), 0, 255) / 255 (dataset.py:356, :370), then cv2
  * BGR2GRAY where flagged (dataset.py:303-306). */
 int vsp_degrade_up_f32(float* out, const uint8_t* lq, const vsp_degrade_item* items, int n, int H, int W, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device-side ingest: Pillow's 8-bit LANCZOS resize (Image.resize(size, LANCZOS)) and a crop, for a ragged batch of decoded RGB images
+ * of different sizes, bit for bit (csrc/resample.hip).  Pillow's resampler is integer arithmetic: per axis and output coordinate a
+ * first source coordinate `xmin`, a tap `count` and fixed-point taps round(k * 2^22); a horizontal then a vertical pass of
+ * clip8((2^21 + sum(pixel * k)) >> 22) with a uint8 image between them.  The tables need libm's sin in float64 and are built on the
+ * host (vspbfr_amd/resample.py lanczos_coeffs); the device does the integer multiply-adds.
+ *
+ *   src      packed source bytes; item i's (sh, sw, 3) uint8 image at byte offset src_off, rows of 3 * sw bytes without padding
+ *   coef     int32; a table for (in, out) at int32 offset o is  xmin[out], count[out], taps[ksize][out]  (tap-major), ksize =
+ *            (int)ceil(3 * max(1, in / out)) * 2 + 1
+ *   work     the uint8 image between the passes: item i's rows row0..row1 of the horizontally resized crop columns at byte offset
+ *            work_off, row stride vsp_lanczos_work_bytes(1, W); private to the call until it has finished on `stream`
+ *   out_u8   (n, H, W, 3) uint8 and / or  out_f32  (n, 3, H, W) fp32 = ((v / 255) - 0.5) / 0.5, three separately rounded operations
+ *            (torchvision's ToTensor + Normalize(0.5, 0.5)); either may be NULL, not both
+ * Only the crop window [x0, x0 + W) x [y0, y0 + H) of the resized (nw, nh) image is computed, and only source rows row0..row1 (the
+ * rows the window's vertical taps read) go through the horizontal pass.  `items` is the table in HOST memory: every entry is checked
+ * (sizes, crop, tap counts, all offsets against src_bytes / coef_ints / work_bytes) before anything is launched; `items_dev` is the
+ * same table in device memory, which the kernels read.  VSP_EINVAL: null pointer, zero size, crop outside the resized image, an
+ * offset outside its buffer.  VSP_ENOTSUP: a side above VSP_RESAMPLE_MAX_SIDE or more than VSP_RESAMPLE_MAX_TAPS taps (a reduction
+ * above 16x): the caller resizes such an image on the host and passes it as a VSP_RESAMPLE_COPY item.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_RESAMPLE_PRECISION_BITS 22 /* Pillow's PRECISION_BITS (32 - 8 - 2) */
+#define VSP_RESAMPLE_MAX_TAPS 97       /* taps per output coordinate: reductions up to 16x */
+#define VSP_RESAMPLE_MAX_SIDE 8192     /* source, resized and output side */
+#define VSP_RESAMPLE_MAX_ITEMS 65535   /* items per launch */
+#define VSP_RESAMPLE_FLIP 1            /* flags: the source is read mirrored (column sw - 1 - x): transpose(FLIP_LEFT_RIGHT) first */
+#define VSP_RESAMPLE_COPY 2            /* flags: the source already has the output size and is copied (sw == nw == W, sh == nh == H) */
+
+typedef struct vsp_resample_item {
+  int64_t src_off;   /* byte offset of the source image in `src` */
+  int64_t work_off;  /* byte offset of the item's intermediate rows in `work`, a multiple of 4 */
+  int64_t hco, vco;  /* int32 offsets of the horizontal (sw -> nw) and the vertical (sh -> nh) table in `coef` */
+  int32_t sw, sh;    /* source size */
+  int32_t nw, nh;    /* resized size */
+  int32_t x0, y0;    /* crop origin inside the resized image */
+  int32_t row0, row1;/* first and last source row the crop's vertical pass reads: ymin[y0] .. ymin[y0+H-1] + count[y0+H-1] - 1 */
+  int32_t hk, vk;    /* ksize of the two tables */
+  int32_t flags;     /* VSP_RESAMPLE_FLIP | VSP_RESAMPLE_COPY */
+  int32_t pad_;
+} vsp_resample_item;
+
+/* bytes of `work` for `rows` intermediate rows of an output of width W (0 for arguments outside the limits) */
+size_t vsp_lanczos_work_bytes(int rows, int W);
+int vsp_lanczos_resize_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, size_t src_bytes, const int32_t* coef, size_t coef_ints,
+                          uint8_t* work, size_t work_bytes, const vsp_resample_item* items, const vsp_resample_item* items_dev, int n,
+                          int H, int W, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@ import os
 # allocations.  Loading this library first would pull /opt/rocm's runtime in and leave two HIP runtimes in one process.
 import torch  # noqa: F401
 
+from .resample import ResampleItem  # vsp_resample_item: defined beside the plan that fills it, importable without the library
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VSPBFR_HIP_LIB", os.path.join(_HERE, "lib", "libvspbfr_hip.so"))
 
@@ -187,12 +189,13 @@ SIGNATURES = {
     "vsp_degrade_jpeg_u8": [_p, _p, _p, _i, _i, _i, _p],
     "vsp_degrade_up_f32": [_p, _p, _p, _i, _i, _i, _p],
     "vsp_pair_stats_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    "vsp_lanczos_resize_u8": [_p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _i, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
           "vsp_winograd_weight_floats": [_i, _i, _i], "vsp_winograd4_weight_floats": [_i, _i], "vsp_winograd4f_weight_floats": [_i, _i],
           "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i],
-          "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i]}
+          "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i], "vsp_lanczos_work_bytes": [_i, _i]}
 
 
 def _load():
@@ -216,7 +219,7 @@ def _load():
     if lib.vsp_abi_version() != ABI_VERSION:
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
-                      (5, ConvWgradParams), (6, DegradeItem)):
+                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -35,6 +35,7 @@ int vsp_struct_size(int which) {
     case 4: return (int)sizeof(vsp_tacc_chain_params);
     case 5: return (int)sizeof(vsp_conv_wgrad_params);
     case 6: return (int)sizeof(vsp_degrade_item);
+    case 7: return (int)sizeof(vsp_resample_item);
     default: return -1;
   }
 }

@@ -1618,6 +1618,26 @@ def degrade_up(lq, items, n, Hh, Ww):
     check(lib.vsp_degrade_up_f32(_ptr(out), _ptr(_u8(lq, "lq")), _ptr(_u8(items, "items")), n, Hh, Ww, _stream()), "degrade_up")
     return out
 
+# ----------------------------------------------------------------------------------------------- device-side ingest
+def lanczos_resize_u8(plan, items, coef, src, u8=True, f32=False):
+    """Pillow-exact LANCZOS resize + crop of one ragged batch (vsp_lanczos_resize_u8, csrc/resample.hip).  plan: the
+    vspbfr_amd.resample.ResamplePlan whose sections `items`, `coef`, `src` (device uint8 tensors, ResamplePlan.pack's layout) were
+    uploaded.  Returns (u8 (n, H, W, 3) uint8 or None, f32 (n, 3, H, W) fp32 or None) on the current stream."""
+    import ctypes as Ct
+    _u8(items, "items"), _u8(coef, "coef"), _u8(src, "src")
+    if not (u8 or f32):
+        raise RuntimeError("lanczos_resize_u8: no output asked for")
+    if items.numel() != Ct.sizeof(plan.items) or coef.numel() != 4 * plan.coef_ints or src.numel() != plan.src_bytes:
+        raise RuntimeError("lanczos_resize_u8: the device sections do not have the plan's sizes")
+    n, Hh, Ww = plan.n, plan.H, plan.W
+    out8 = torch.empty((n, Hh, Ww, 3), device=src.device, dtype=torch.uint8) if u8 else None
+    outf = torch.empty((n, 3, Hh, Ww), device=src.device, dtype=torch.float32) if f32 else None
+    work = torch.empty(max(plan.work_bytes // 4, 1), device=src.device, dtype=torch.int32)
+    check(lib.vsp_lanczos_resize_u8(_ptr(out8), _ptr(outf), _ptr(src), plan.src_bytes, _ptr(coef), plan.coef_ints, _ptr(work),
+                                    plan.work_bytes, Ct.cast(plan.items, Ct.c_void_p), _ptr(items), n, Hh, Ww, _stream()),
+          "lanczos_resize_u8")
+    return out8, outf
+
 
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""

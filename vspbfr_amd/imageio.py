@@ -5,7 +5,11 @@ save_image(normalize=True, range=(-1, 1))).
 Decode/resize stay on the host (PIL, exactly the reference's LANCZOS-resize-to-cover + centre crop, so pixels match);
 the quantiser to 8 bits + NCHW->NHWC transpose runs on the device (vsp_quantize_u8_nhwc) so a restored batch crosses
 PCIe as 0.75 MB/image of uint8 instead of 3 MB of fp32, and PNG encoding happens on a thread pool while the next batch
-is already on the GPU."""
+is already on the GPU.
+
+`DeviceRestoreLoader` is the opt-in device ingest of the same dataset (`restoration_metrics --ingest device`): only the decode stays on the
+host, on a thread pool one batch ahead; the LANCZOS resize, the crop and the normalisation run on the device (vspbfr_amd.resample,
+vsp_lanczos_resize_u8) and give the bits `RestoreTestSet.__getitem__` gives."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -82,6 +86,60 @@ class RestoreTestSet:
         if self.hq is None:
             return load_image(self.lq[idx], self.im_size)
         return load_pair(self.lq[idx], self.hq[idx], self.im_size)
+
+
+class DeviceRestoreLoader:
+    """RestoreTestSet with the resize on the device: iterates over (idx, low, gts) for the items lo..hi in batches, `low` and `gts`
+    (B, 3, H, W) fp32 tensors on `device` (gts None without ground truth), bit-equal to stacking `dataset[i]`.  Only the decode
+    (`Image.open(...).convert("RGB")`) stays on the host, on a pool of `threads` workers, one batch ahead of the consumer; a batch
+    goes up as one pinned ragged buffer and vsp_lanczos_resize_u8 resizes, crops and normalises it (vspbfr_amd.resample)."""
+
+    def __init__(self, dataset, batch, device, lo=0, hi=None, threads=8):
+        self.ds, self.B, self.device = dataset, int(batch), torch.device(device)
+        self.lo, self.hi = int(lo), len(dataset) if hi is None else int(hi)
+        if self.B < 1 or not 0 <= self.lo <= self.hi <= len(dataset):
+            raise ValueError(f"DeviceRestoreLoader: batch {batch}, items {lo}..{hi} of {len(dataset)}")
+        self.threads = max(1, int(threads))
+
+    @staticmethod
+    def _decode(path):
+        from PIL import Image
+        return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+    def _host(self, pool, idx):
+        """host half of a batch: decode on the pool, plan and pack the ragged upload (the LQ items first, then the HQ items)"""
+        from .resample import ResamplePlan, cover_geometry
+        paths = [self.ds.lq[i] for i in idx] + ([self.ds.hq[i] for i in idx] if self.ds.hq is not None else [])
+        arrs = list(pool.map(self._decode, paths))
+        n = len(idx)
+        H, W = self.ds.im_size
+        targets, origins = [], []
+        for k, a in enumerate(arrs):
+            ref = arrs[n + k % n] if self.ds.hq is not None else a      # the HQ image's size decides (load_pair)
+            nw, nh, box = cover_geometry(ref.shape[1], ref.shape[0], (H, W))
+            if (nw, nh) == (ref.shape[1], ref.shape[0]) == (W, H) and a.shape[:2] != (H, W):
+                raise ValueError(f"{paths[k]}: {a.shape[1]}x{a.shape[0]} beside a ground truth of the target size (load_pair keeps both as they are)")
+            targets.append((nw, nh))
+            origins.append(box[:2])
+        plan = ResamplePlan(arrs, targets, origins, (H, W))
+        plan.pack()
+        return plan
+
+    def __iter__(self):
+        starts = list(range(self.lo, self.hi, self.B))
+        if not starts:
+            return
+        batches = [list(range(s, min(s + self.B, self.hi))) for s in starts]
+        with ThreadPoolExecutor(max_workers=self.threads) as pool, ThreadPoolExecutor(max_workers=1) as ahead:
+            nxt = ahead.submit(self._host, pool, batches[0])
+            for k, idx in enumerate(batches):
+                plan = nxt.result()
+                if k + 1 < len(batches):
+                    nxt = ahead.submit(self._host, pool, batches[k + 1])
+                with torch.cuda.device(self.device):
+                    _, out = plan.run(self.device, u8=False, f32=True)
+                n = len(idx)
+                yield idx, out[:n], (out[n:] if self.ds.hq is not None else None)
 
 
 def output_name(eval_dir, index, rank, data_name, kind):

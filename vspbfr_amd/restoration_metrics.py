@@ -25,6 +25,31 @@ from .restoration_test import get_store_data
 from .restorenet import Restoration_net
 
 
+def _host_batches(args, data, lo, hi, device):
+    """--ingest host: decode, LANCZOS resize and crop on the main thread (PIL), as vspbfr_amd.restoration_test does"""
+    for start in range(lo, hi, args.batch):
+        idx = list(range(start, min(start + args.batch, hi)))
+        items = [data[i] for i in idx]
+        gts = None
+        if data.hq is not None:
+            gts = torch.stack([it[1] for it in items])
+            items = [it[0] for it in items]
+        yield idx, torch.stack(items).to(device, non_blocking=True), gts
+
+
+def _batches(args, data, lo, hi, device):
+    """(idx, low on the device, gts or None) per batch; --debug stops after 11 batches"""
+    if getattr(args, "ingest", "host") == "device":
+        from .imageio import DeviceRestoreLoader
+        it = DeviceRestoreLoader(data, args.batch, device, lo, hi)
+    else:
+        it = _host_batches(args, data, lo, hi, device)
+    for k, b in enumerate(it):
+        if args.debug and k > 10:
+            break
+        yield b
+
+
 def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, device, rank=0, world=1):
     data = RestoreTestSet(lq_root, None if hq_root == "None" else hq_root, (args.size, args.size))
     lo, hi = shard_range(len(data), rank, world)
@@ -36,16 +61,7 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
         evaluator = Evaluator(args.ssim_window, *args.scorers)
     print("testing!!! len:%d (rank %d handles %d..%d)" % (len(data), rank, lo, hi))
     with torch.no_grad():
-        for start in range(lo, hi, args.batch):
-            idx = list(range(start, min(start + args.batch, hi)))
-            if args.debug and (start - lo) // args.batch > 10:
-                break
-            items = [data[i] for i in idx]
-            gts = None
-            if data.hq is not None:
-                gts = torch.stack([it[1] for it in items])
-                items = [it[0] for it in items]
-            low = torch.stack(items).to(device, non_blocking=True)
+        for idx, low, gts in _batches(args, data, lo, hi, device):
             out = pipe(low)
             u8 = {}
             for kind, t in (("restore", out["restored"]), ("low", low), ("sample", out["style_sample"]), ("gt", gts)):
@@ -84,6 +100,9 @@ def main(argv=None):
     ap.add_argument("--metrics", action="store_true",
                     help="extension: score *_restore.png against *_gt.png on the device (PSNR, SSIM; LPIPS / ID with the weights "
                          "below) and write metrics_<rank>.json beside the PNGs; needs a ground-truth root for every dataset")
+    ap.add_argument("--ingest", choices=["host", "device"], default="host",
+                    help="extension: host = PIL decode + LANCZOS resize + crop on the main thread (as restoration_test); device = decode on "
+                         "a thread pool, resize and crop on the GPU (imageio.DeviceRestoreLoader), the same bytes")
     ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11",
                     help="extension: SSIM window (gauss11: Wang et al.; uniform7: scikit-image's default, the reference's dssim)")
     ap.add_argument("--lpips_weights", type=str, default=None, help="extension: LIN[,VGG] weight files; adds the lpips column")

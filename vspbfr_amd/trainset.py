@@ -15,6 +15,9 @@ for ImageFolder_restore); `*2 - 1` (and `/127.5 - 1` for a uint8 gt) maps them a
 Every random draw of a sample is a function of (seed, epoch, dataset index, slot) (degrade.sample_rng), so a sample is read and degraded
 identically whichever rank serves it at whatever world size.  The shift augmentation of the free-form class is dead code (shift_prob 0)
 and left out.
+
+`DegradeLoader(..., resize="device")` keeps only the decode on the pool: the flip, the LANCZOS cover resize and the random crop run on the
+device (vspbfr_amd.resample), with the same draws in the same order, and the batches are bit-equal to the default `resize="host"`.
 """
 import math
 from concurrent.futures import ThreadPoolExecutor
@@ -61,6 +64,23 @@ class _Folder:
             img = img.crop((wi, hi, wi + tw, hi + th))
         return np.asarray(img, dtype=np.uint8)
 
+    def load_raw(self, idx, rng):
+        """`load` up to the decode, for the device resize: (uint8 (h, w, 3) as decoded, flip, (nw, nh), (x0, y0)).  The draws from `rng`
+        keep the order of `load` -- flip, crop row, crop column; the crop draws need only the resized size, which cover_geometry gives."""
+        from PIL import Image
+        from .resample import cover_geometry
+        img = Image.open(self.frame[idx % len(self.frame)]).convert("RGB")
+        flip = bool(self.flip and int(rng.integers(0, 2)) == 1)
+        w, h = img.size
+        th, tw = self.im_size
+        nw, nh, _ = cover_geometry(w, h, self.im_size)
+        hi = wi = 0
+        if h != th or w != tw:
+            hr, wr = nh - th, nw - tw
+            hi = int(rng.integers(0, hr + 1)) if hr > 0 else 0
+            wi = int(rng.integers(0, wr + 1)) if wr > 0 else 0
+        return np.asarray(img, dtype=np.uint8), flip, (nw, nh), (wi, hi)
+
     def draws(self, epoch, idx, seed=0):
         """Host draws of one sample: (grey, [LQParams per LQ image]).  The flip / crop draws come from the same slot-0 generator in
         `load`, after the grey draw."""
@@ -101,9 +121,12 @@ class DegradeLoader:
     """Batches of `dataset` for one rank: iterate for an endless stream (the reference's `sample_data`), or `epoch(e)` for one pass.
     Yields (lq1, lq2, gt) for ImageFolder_restore_free_form and (lq, gt uint8) for ImageFolder_restore, device tensors (B, 3, H, W)."""
 
-    def __init__(self, dataset, batch_size, device=None, seed=0, rank=0, world_size=1, threads=4, drop_last=True):
+    def __init__(self, dataset, batch_size, device=None, seed=0, rank=0, world_size=1, threads=4, drop_last=True, resize="host"):
         if len(dataset) == 0:
             raise ValueError(f"no images under {dataset.root}")
+        if resize not in ("host", "device"):
+            raise ValueError(f"resize must be 'host' or 'device' (got {resize!r})")
+        self.resize = resize   # "device": the pool only decodes; flip, LANCZOS resize and crop run on the device (vspbfr_amd.resample)
         self.ds, self.B, self.seed = dataset, int(batch_size), int(seed)
         self.rank, self.world = int(rank), int(world_size)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -116,12 +139,18 @@ class DegradeLoader:
 
     def _decode(self, epoch, idx):
         grey, lqs, rng = self.ds.draws(epoch, idx, self.seed)
-        return grey, lqs, self.ds.load(idx, rng)
+        return grey, lqs, (self.ds.load(idx, rng) if self.resize == "host" else self.ds.load_raw(idx, rng))
 
     def _host(self, epoch, idxs):
-        """host half of a batch: decode on the pool, stack into pinned memory"""
+        """host half of a batch: decode on the pool, stack into pinned memory (resize="device": pack the ragged sources and their plan)"""
         got = list(self.pool.map(lambda i: self._decode(epoch, int(i)), idxs))
         Hh, Ww = self.ds.im_size
+        if self.resize == "device":
+            from .resample import ResamplePlan
+            raw = [g[2] for g in got]
+            plan = ResamplePlan([r[0] for r in raw], [r[2] for r in raw], [r[3] for r in raw], (Hh, Ww), flips=[r[1] for r in raw])
+            plan.pack()
+            return got, plan
         host = torch.empty((len(got), Hh, Ww, 3), dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         for b, (_, _, img) in enumerate(got):
@@ -131,7 +160,7 @@ class DegradeLoader:
     def _device(self, epoch, idxs, got, host):
         """device half: upload, gt / 255, the degradation chain, grey gt where drawn"""
         B, (Hh, Ww) = len(got), self.ds.im_size
-        hwc = host.to(self.device, non_blocking=True)
+        hwc = host.to(self.device, non_blocking=True) if self.resize == "host" else host.run(self.device, u8=True)[0]
         gt = H.degrade_gt(hwc=hwc)
         n_lq = self.ds.n_lq
         lqs = [got[b][1][s] for s in range(n_lq) for b in range(B)]          # slot-major: lq1 of every sample, then lq2
