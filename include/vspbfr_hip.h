@@ -760,6 +760,42 @@ int vsp_lanczos_resize_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, s
                           uint8_t* work, size_t work_bytes, const vsp_resample_item* items, const vsp_resample_item* items_dev, int n,
                           int H, int W, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Device-side PNG encoder: row filters + deflate of a (B, H, W, C) uint8 batch (csrc/png.hip), 8 bits per sample, C = 3 (colour type
+ * 2) or 1 (colour type 0), no interlace.  The device writes each image's zlib payload in pieces; the host puts the two-byte zlib header
+ * in front, the combined Adler-32 behind, and frames the PNG chunks (vspbfr_amd/png.py assemble).  tests/png_ref.py restates every step
+ * in NumPy; the device output equals it byte for byte.
+ *
+ *   filters    per row the filter type 0..4 with the smallest sum of |residual as int8|, ties to the lowest type; the row above a
+ *              segment's first row is the image's real previous row
+ *   segments   the filtered stream (H rows of 1 + C * W bytes) is cut into segments of VSP_PNG_SEG_ROWS rows.  A segment is compressed on
+ *              its own into ONE deflate block: dynamic Huffman, or a stored block when the coded segment would not be smaller.  A
+ *              non-final segment ends with an empty stored block (3 zero bits, padding, 00 00 FF FF) and so on a byte boundary; the
+ *              last segment's block carries BFINAL.  The zlib payload is the concatenation of the segments
+ *   tokens     literals and distance-1 matches of length 3..258: a maximal stretch of bytes equal to their predecessor inside the
+ *              segment is cut into chunks of 258 from its start; a chunk below 3 is literals
+ *   codes      literal/length code limited to 15 bits, code-length code to 7: symbols sorted by (count, symbol), Huffman's two-queue
+ *              merge taking a leaf before an internal node of equal weight, depths clipped and repaired as zlib does, lengths handed
+ *              out longest first in sorted order, canonical codes.  One distance symbol (0) of length 1, or 0 when there is no match
+ *   out        image i at byte i * out_capacity, its segment k at k * vsp_png_segment_bound(VSP_PNG_SEG_ROWS, W, C) inside it,
+ *              seg_bytes[i * nseg + k] bytes long (never above vsp_png_segment_bound(rows of that segment, W, C): the stored form);
+ *              nseg = ceil(H / VSP_PNG_SEG_ROWS).  Bytes of a slot behind a segment's end, rounded up to 4, are not written
+ *   seg_adler  [2 * (i * nseg + k)] = sum of the segment's n filtered bytes, [+ 1] = sum of (n - j) * byte[j], both mod 65521; in order
+ *              b = (b + n * a + part1) mod 65521, a = (a + part0) mod 65521 from (a, b) = (1, 0) gives zlib's Adler-32 b << 16 | a
+ * src is the contiguous (B, H, W, C) tensor; out, seg_bytes, seg_adler and out_capacity are 4-byte aligned; out_capacity >=
+ * vsp_png_bound(H, W, C).  Every size is checked on the host before the single launch.  VSP_ENOTSUP: C * W above VSP_PNG_MAX_ROW_BYTES,
+ * H above VSP_PNG_MAX_H or B above VSP_PNG_MAX_BATCH (the caller encodes such images on the host); VSP_EINVAL: C not 1 or 3, a zero
+ * size, a null or misaligned pointer, out_capacity below the bound.  The bounds return 0 for arguments outside the limits.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_PNG_SEG_ROWS 8           /* rows per segment: 8 x 3073 filtered bytes, the bit buffer and the code tables fit 64 KB of LDS */
+#define VSP_PNG_MAX_ROW_BYTES 3072   /* C * W: W <= 1024 for RGB */
+#define VSP_PNG_MAX_H 32768
+#define VSP_PNG_MAX_BATCH 65535
+size_t vsp_png_segment_bound(int rows, int W, int C);
+size_t vsp_png_bound(int H, int W, int C);
+int vsp_png_encode_u8(uint8_t* out, size_t out_capacity, int32_t* seg_bytes, uint32_t* seg_adler, const uint8_t* src, int B, int H, int W,
+                      int C, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1639,6 +1639,31 @@ def lanczos_resize_u8(plan, items, coef, src, u8=True, f32=False):
     return out8, outf
 
 
+def png_encode(u8, guard=0):
+    """Row filters + deflate of a (B, H, W, C) uint8 batch on the current stream (vsp_png_encode_u8, csrc/png.hip; C = 3 or 1).  Returns
+    (out (B, capacity + guard) uint8, seg_bytes (B, nseg) int32, seg_adler (B, nseg, 2) int32 bit patterns of uint32, slot): image i's
+    segment k is out[i, k * slot : k * slot + seg_bytes[i, k]]; vspbfr_amd.png.assemble turns them into files.  guard: extra bytes behind
+    every image's capacity that the kernel must leave alone (tests).  A shape above the header's limits raises NotImplementedError."""
+    _u8(u8, "u8")
+    if u8.dim() != 4:
+        raise RuntimeError("png_encode: u8 must be (B, H, W, C)")
+    B, Hh, Ww, Cc = u8.shape
+    if Cc not in (1, 3) or B < 1 or Hh < 1 or Ww < 1:
+        raise RuntimeError(f"png_encode: shape {tuple(u8.shape)}")
+    cap, slot = lib.vsp_png_bound(Hh, Ww, Cc), lib.vsp_png_segment_bound(8, Ww, Cc)
+    if cap == 0 or B > 65535:
+        raise NotImplementedError(f"png_encode: shape {tuple(u8.shape)} above the limits of vsp_png_encode_u8")
+    if guard % 4:
+        raise RuntimeError("png_encode: guard must be a multiple of 4")
+    nseg = (Hh + 7) // 8
+    out = torch.full((B, cap + guard), 0xA5, device=u8.device, dtype=torch.uint8) if guard else torch.empty((B, cap), device=u8.device,
+                                                                                                       dtype=torch.uint8)
+    seg_bytes = torch.empty((B, nseg), device=u8.device, dtype=torch.int32)
+    seg_adler = torch.empty((B, nseg, 2), device=u8.device, dtype=torch.int32)
+    check(lib.vsp_png_encode_u8(_ptr(out), cap + guard, _ptr(seg_bytes), _ptr(seg_adler), _ptr(u8), B, Hh, Ww, Cc, _stream()), "png_encode")
+    return out, seg_bytes, seg_adler, slot
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types

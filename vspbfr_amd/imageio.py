@@ -9,7 +9,10 @@ is already on the GPU.
 
 `DeviceRestoreLoader` is the opt-in device ingest of the same dataset (`restoration_metrics --ingest device`): only the decode stays on the
 host, on a thread pool one batch ahead; the LANCZOS resize, the crop and the normalisation run on the device (vspbfr_amd.resample,
-vsp_lanczos_resize_u8) and give the bits `RestoreTestSet.__getitem__` gives."""
+vsp_lanczos_resize_u8) and give the bits `RestoreTestSet.__getitem__` gives.
+
+`PngWriter(encode="device")` is the opt-in device encoder of the other end (`restoration_metrics --encode device`): row filters and deflate run
+on the device (vspbfr_amd.png, vsp_png_encode_u8) and the worker threads only frame and write the files; the pixels are those of the host path."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -148,11 +151,15 @@ def output_name(eval_dir, index, rank, data_name, kind):
 
 
 class PngWriter:
-    """Device-side quantisation + asynchronous PNG encoding."""
+    """Device-side quantisation + asynchronous PNG encoding.  encode="host": PIL encodes on the worker threads.  encode="device": the
+    row filters and the deflate stream are made on the device (vspbfr_amd.png, csrc/png.hip); the workers frame and write the files."""
 
-    def __init__(self, workers=8):
+    def __init__(self, workers=8, encode="host"):
+        if encode not in ("host", "device"):
+            raise ValueError(f"PngWriter: encode {encode!r}")
         self.pool = ThreadPoolExecutor(max_workers=workers)
         self.pending = []
+        self.encode = encode
 
     def submit(self, batch, paths):
         """batch: (B, 3, H, W) fp32 on the device in [-1, 1] (values outside are clamped like save_image does), or the
@@ -160,6 +167,12 @@ class PngWriter:
         vspbfr_amd.metrics scores)."""
         from . import hip_ops as H
         u8 = batch if batch.dtype == torch.uint8 else H.quantize_u8_nhwc(batch.contiguous(), -1.0, 1.0)
+        if self.encode == "device":
+            from . import png
+            if png.kernel_serves(u8.shape):
+                job = png.enqueue(u8)        # encoder + asynchronous copies on the current stream; no synchronisation here
+                self.pending.append(self.pool.submit(self._write, job, list(paths)))
+                return u8
         host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
         host.copy_(u8, non_blocking=True)
         ev = torch.cuda.Event()
@@ -174,6 +187,12 @@ class PngWriter:
         arr = host.numpy()
         for i, p in enumerate(paths):
             Image.fromarray(arr[i]).save(p)
+
+    @staticmethod
+    def _write(job, paths):
+        for p, data in zip(paths, job.files()):
+            with open(p, "wb") as f:
+                f.write(data)
 
     def drain(self):
         for f in self.pending:

@@ -1,7 +1,7 @@
 """The inference CLI with its output scored against ground truth on the device.
 
     python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
-        --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
+        [--ingest host|device] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
 
 `vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
 puts it under this repository's rule that a feature leaves every existing `*_test.py` / `test_*.py` file as it is.  This module
@@ -54,7 +54,7 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
     data = RestoreTestSet(lq_root, None if hq_root == "None" else hq_root, (args.size, args.size))
     lo, hi = shard_range(len(data), rank, world)
     os.makedirs(eval_dict, exist_ok=True)
-    writer = PngWriter()
+    writer = PngWriter(encode=getattr(args, "encode", "host"))
     evaluator = None
     if args.metrics:
         from .metrics import Evaluator
@@ -103,6 +103,9 @@ def main(argv=None):
     ap.add_argument("--ingest", choices=["host", "device"], default="host",
                     help="extension: host = PIL decode + LANCZOS resize + crop on the main thread (as restoration_test); device = decode on "
                          "a thread pool, resize and crop on the GPU (imageio.DeviceRestoreLoader), the same bytes")
+    ap.add_argument("--encode", choices=["host", "device"], default="host",
+                    help="extension: host = PIL encodes the PNGs on the writer's threads (as restoration_test); device = row filters and deflate "
+                         "on the GPU (vspbfr_amd.png), the threads frame and write; other file bytes, the same pixels")
     ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11",
                     help="extension: SSIM window (gauss11: Wang et al.; uniform7: scikit-image's default, the reference's dssim)")
     ap.add_argument("--lpips_weights", type=str, default=None, help="extension: LIN[,VGG] weight files; adds the lpips column")
