@@ -314,15 +314,16 @@ __global__ __launch_bounds__(WG_NT, S != 0 ? 2 : 1) void conv_wgrad_kernel(const
   }
 }
 
-// dw[i] (+)= sum over the split copies
+// dw[i] (+)= sum over the split copies.  Copy c starts at work + c n: 16-byte aligned only when n is a multiple of 4, so the copies are
+// read as 4-byte-aligned vectors (the same 16-byte load instruction; the type no longer promises an alignment that odd copies lack).
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(float* __restrict__ dw, const float* __restrict__ work, int64_t n, int copies,
                                                             int accumulate) {
   const int64_t n4 = n >> 2;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
     float4 a = accumulate ? reinterpret_cast<const float4*>(dw)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     for (int c = 0; c < copies; ++c) {
-      const float4 v = reinterpret_cast<const float4*>(work + (int64_t)c * n)[i];
-      a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+      const f32x4u v = reinterpret_cast<const f32x4u*>(work + (int64_t)c * n)[i];
+      a.x += v[0]; a.y += v[1]; a.z += v[2]; a.w += v[3];
     }
     reinterpret_cast<float4*>(dw)[i] = a;
   }
@@ -575,9 +576,10 @@ extern "C" int vsp_conv2d_wgrad_f32(const vsp_conv_wgrad_params* pp, vsp_stream_
   const size_t dw_bytes = (size_t)dw_elems * sizeof(float);
   hipStream_t st = vsp::as_stream(stream);
   const bool use_work = q.work != nullptr && q.work_floats > 0;
-  if (!q.accumulate && (!use_work || q.B == 0 || q.OH == 0 || q.OW == 0) && hipMemsetAsync(q.dw, 0, dw_bytes, st) != hipSuccess)
-    return vsp::fail(VSP_ELAUNCH, "conv2d_wgrad: memset failed");
-  if (q.B == 0 || q.OH == 0 || q.OW == 0) return VSP_OK;
+  if (q.B == 0 || q.OH == 0 || q.OW == 0) {   // nothing to sum
+    if (!q.accumulate && hipMemsetAsync(q.dw, 0, dw_bytes, st) != hipSuccess) return vsp::fail(VSP_ELAUNCH, "conv2d_wgrad: memset failed");
+    return VSP_OK;
+  }
   VSP_REQUIRE(q.x && q.dy, "conv2d_wgrad: null input");
   k.x = q.x; k.dy = q.dy; k.dw = q.dw; k.xs = q.x_scale; k.dys = q.dy_scale;
   k.scale = q.dw_scale != 0.f ? q.dw_scale : 1.f;
@@ -599,7 +601,7 @@ extern "C" int vsp_conv2d_wgrad_f32(const vsp_conv_wgrad_params* pp, vsp_stream_
     if (copies_fit) {   // every (copy, element) is written exactly once: no memset
       k.work = q.work;
       k.dw_elems = dw_elems;
-    } else if (!q.accumulate && use_work && hipMemsetAsync(q.dw, 0, dw_bytes, st) != hipSuccess) {
+    } else if (!q.accumulate && hipMemsetAsync(q.dw, 0, dw_bytes, st) != hipSuccess) {   // atomics (no workspace, or one too small)
       return vsp::fail(VSP_ELAUNCH, "conv2d_wgrad: memset failed");
     }
     dim3 grid((unsigned)ranges, (unsigned)q.B, (unsigned)co_blocks);
@@ -641,6 +643,8 @@ extern "C" int vsp_conv2d_wgrad_f32(const vsp_conv_wgrad_params* pp, vsp_stream_
   }
   const size_t lds = ((size_t)co_t * DPITCH + (size_t)ci_t * k.plane) * sizeof(float);
   VSP_REQUIRE(lds <= kMaxLds, "conv2d_wgrad: row segment with halo does not fit LDS (dilation %d)", dmax);
+  // the atomics add into dw itself: it starts from zero, and only now -- a refused call leaves dw as it was
+  if (!use_work && !q.accumulate && hipMemsetAsync(q.dw, 0, dw_bytes, st) != hipSuccess) return vsp::fail(VSP_ELAUNCH, "conv2d_wgrad: memset failed");
   dim3 grid((unsigned)split, (unsigned)tiles, (unsigned)q.G);
   const bool k3 = q.KH == 3;
   int rc;
