@@ -796,6 +796,37 @@ size_t vsp_png_bound(int H, int W, int C);
 int vsp_png_encode_u8(uint8_t* out, size_t out_capacity, int32_t* seg_bytes, uint32_t* seg_adler, const uint8_t* src, int B, int H, int W,
                       int C, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * No-reference quality: the NIQE features (Mittal, Soundararajan, Bovik 2013) of B uint8 RGB images (B, H, W, 3), one launch,
+ * no host synchronisation (csrc/niqe.hip).
+ *   luma       Y = round-half-even(16 + (65.481 R + 128.553 G + 24.966 B) / 255), exact in integers; crop_border pixels are cut
+ *              from every side, then the image is cut at the top left to multiples of 96: nby x nbx blocks, nblk = nby * nbx >= 2
+ *   scales     s = 1: Y, blocks of 96; s = 2: the bicubic antialiased half-size image, taps [-3 -9 29 111 111 29 -9 -3] / 256 at
+ *              input rows 2i - 3 .. 2i + 4, symmetric reflection (-1 -> 0), rows then columns, blocks of 48
+ *   MSCN       mu = 7 x 7 Gaussian (sigma 7/6, normalised, separable), edge replicate on that scale's own image;
+ *              sigma_loc = sqrt|G * x^2 - mu^2|; v = (x - mu) / (sigma_loc + 1)
+ *   maps       per block and scale five maps: v, and v * roll(v, s) for s = (0,1), (1,0), (1,1), (1,-1), the roll circular in the block
+ *   moments    per map six raw moments in float64: n-, sum- v^2, n+, sum+ v^2, sum |v|, sum v^2 (a zero lies on neither side);
+ *              moments (B, nblk, 2, 5, 6), may be NULL
+ *   features   (B, nblk, 36) float64, scale 1 then scale 2, per scale [alpha, (bl + br) / 2] of v and [alpha, (br - bl) *
+ *              G(2/alpha) / G(1/alpha), bl, br] of each product, from the asymmetric generalised Gaussian fit by moments:
+ *              ls = sqrt(sum- / n-), rs = sqrt(sum+ / n+), g = ls / rs, rhat = mean|v|^2 / mean v^2,
+ *              rnorm = rhat (g^3 + 1)(g + 1) / (g^2 + 1)^2, alpha = the grid point whose r is nearest rnorm (the first of equals),
+ *              b = std * sqrt(G(1/alpha) / G(3/alpha)).  A map with an empty side gives NaN
+ *   sharpness  (B, nblk) float: the mean sigma_loc of the scale-1 block (what the pristine-model fit selects blocks by)
+ *   rgam_table 4 x 9801 float64 on the device, built once by the caller for gamma_k = 0.2 + 0.001 k: gamma, r(gamma) = G(2/gamma)^2 /
+ *              (G(1/gamma) G(3/gamma)), sqrt(G(1/gamma) / G(3/gamma)), G(2/gamma) / G(1/gamma)
+ *   work       vsp_niqe_work_bytes(...) bytes; 0 in this version (every reduction ends in the block's own workgroup), may be NULL
+ * A block's bits depend on its own pixels only: not on B, the position in the batch, or the launch.
+ * VSP_EINVAL, nothing written: crop_border < 0, fewer than two blocks left, a null features / sharpness / img / rgam_table.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_NIQE_BLOCK 96
+#define VSP_NIQE_FEATURES 36
+#define VSP_NIQE_GAMMAS 9801
+size_t vsp_niqe_work_bytes(int B, int H, int W, int crop_border);
+int vsp_niqe_features_u8(double* features, double* moments_or_null, float* sharpness, const uint8_t* img, int B, int H, int W,
+                         int crop_border, const double* rgam_table, void* work, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,13 +191,15 @@ SIGNATURES = {
     "vsp_pair_stats_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
     "vsp_lanczos_resize_u8": [_p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _i, _i, _p],
     "vsp_png_encode_u8": [_p, C.c_size_t, _p, _p, _p, _i, _i, _i, _i, _p],
+    "vsp_niqe_features_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
           "vsp_winograd_weight_floats": [_i, _i, _i], "vsp_winograd4_weight_floats": [_i, _i], "vsp_winograd4f_weight_floats": [_i, _i],
           "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i],
           "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i], "vsp_lanczos_work_bytes": [_i, _i],
-          "vsp_png_segment_bound": [_i, _i, _i], "vsp_png_bound": [_i, _i, _i]}
+          "vsp_png_segment_bound": [_i, _i, _i], "vsp_png_bound": [_i, _i, _i],
+          "vsp_niqe_work_bytes": [_i, _i, _i, _i]}
 
 
 def _load():

@@ -1393,6 +1393,56 @@ def pair_stats_u8(a, b, window="gauss11"):
     return sse, ssim
 
 
+NIQE_BLOCK, NIQE_FEATURES, NIQE_GAMMAS = 96, 36, 9801   # include/vspbfr_hip.h VSP_NIQE_*
+_niqe_tables = {}
+
+
+def niqe_gamma_table():
+    """(4, 9801) float64 on the host, rows gamma_k = 0.2 + 0.001 k, r(gamma) = G(2/g)^2 / (G(1/g) G(3/g)), sqrt(G(1/g) / G(3/g)) and
+    G(2/g) / G(1/g): what the feature kernel looks its shape parameter up in (vsp_niqe_features_u8 rgam_table).  Pure host code."""
+    import math
+    rows = ([], [], [], [])
+    for k in range(NIQE_GAMMAS):
+        g = 0.2 + 0.001 * k
+        g1, g2, g3 = math.gamma(1.0 / g), math.gamma(2.0 / g), math.gamma(3.0 / g)
+        for row, v in zip(rows, (g, g2 * g2 / (g1 * g3), math.sqrt(g1 / g3), g2 / g1)):
+            row.append(v)
+    return torch.tensor(rows, dtype=torch.float64)
+
+
+def niqe_blocks(H, W, crop_border=0):
+    """(rows, columns) of 96 x 96 blocks of an H x W image after `crop_border` -- pure host code"""
+    return max(H - 2 * crop_border, 0) // NIQE_BLOCK, max(W - 2 * crop_border, 0) // NIQE_BLOCK
+
+
+def niqe_features_u8(img, crop_border=0, with_moments=False):
+    """img: (B, H, W, 3) uint8 -> (features float64 (B, nblk, 36), sharpness float32 (B, nblk)[, moments float64 (B, nblk, 2, 5, 6)])
+    on the image's device and the current stream, one launch, without synchronising (vsp_niqe_features_u8; the gamma table is
+    built once per device)."""
+    img = _req_u8(img, "img")
+    if img.dim() != 4 or img.shape[3] != 3:
+        raise RuntimeError(f"niqe_features_u8: img must be (B, H, W, 3) uint8 RGB (got {tuple(img.shape)})")
+    B, Hh, Ww = (int(v) for v in img.shape[:3])
+    crop_border = int(crop_border)
+    nby, nbx = niqe_blocks(Hh, Ww, crop_border)
+    if crop_border < 0 or nby * nbx < 2:
+        raise RuntimeError(f"niqe_features_u8: a {Hh} x {Ww} image with crop_border {crop_border} has fewer than two 96 x 96 blocks")
+    table = _niqe_tables.get(img.device)
+    if table is None:
+        table = _niqe_tables[img.device] = niqe_gamma_table().to(img.device)
+    nblk = nby * nbx
+    feats = torch.empty(B, nblk, NIQE_FEATURES, device=img.device, dtype=torch.float64)
+    sharp = torch.empty(B, nblk, device=img.device, dtype=torch.float32)
+    mom = torch.empty(B, nblk, 2, 5, 6, device=img.device, dtype=torch.float64) if with_moments else None
+    nwork = int(lib.vsp_niqe_work_bytes(B, Hh, Ww, crop_border))
+    work = torch.empty((nwork + 7) // 8, device=img.device, dtype=torch.float64) if nwork else None
+    check(lib.vsp_niqe_features_u8(C.c_void_p(feats.data_ptr()), C.c_void_p(mom.data_ptr()) if with_moments else None,
+                                   C.c_void_p(sharp.data_ptr()), C.c_void_p(img.data_ptr()), B, Hh, Ww, crop_border,
+                                   C.c_void_p(table.data_ptr()), C.c_void_p(work.data_ptr()) if nwork else None, _stream()),
+          "niqe_features_u8")
+    return (feats, sharp, mom) if with_moments else (feats, sharp)
+
+
 # ----------------------------------------------------------------------------------------------- keyed random tensors
 # segment ids of the path's draws (they enter the Philox counter: a tensor keeps its values whatever else is drawn with it)
 SEG_LQ, SEG_XT, SEG_Z = 1, 2, 3           # synthetic LQ batch (bench), x_T (ldm/ddpm.py:423), z (restoration_test.py:77-82; +1: second mixing code)

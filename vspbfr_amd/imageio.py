@@ -34,6 +34,12 @@ def list_images(root):
     return out
 
 
+def load_rgb_u8(path):
+    """An image file as the (H, W, 3) uint8 host tensor the scoring tools batch: PIL decode, converted to RGB, no resize."""
+    from PIL import Image
+    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy())
+
+
 def _to_tensor(img):
     """ToTensor + Normalize(0.5, 0.5) (restoration_test.py:89-94): uint8 HWC -> float32 CHW in [-1, 1]."""
     a = np.asarray(img, dtype=np.uint8)

@@ -1,5 +1,6 @@
 """Full-reference image quality of restored faces against ground truth, measured on the device: PSNR, SSIM and -- with
-user-supplied weights -- LPIPS and identity similarity.
+user-supplied weights -- LPIPS and identity similarity; and, for runs without ground truth, the no-reference NIQE score of the
+restored image alone against a user-supplied pristine model (vspbfr_amd/niqe.py).
 
 The reference has the pixel metrics as host code for one image at a time (my_lpips.psnr / my_lpips.dssim,
 my_lpips/__init__.py:57-61; networks_basic.DSSIM / L2, networks_basic.py:143-180) and never calls them.  Here they come from
@@ -15,6 +16,7 @@ import math
 import torch
 
 WINDOWS = ("gauss11", "uniform7")
+COLUMNS = ("psnr", "ssim", "lpips", "id", "niqe")
 PEAK = 255.0
 
 
@@ -69,10 +71,10 @@ def summarize(rows, dataset=None, window="gauss11"):
     """The report of a list of per-image rows: mean of every column present (mean PSNR = mean of the per-image PSNR over the
     pairs that have one; identical pairs are counted in `psnr_infinite`)."""
     rows = sorted(rows, key=lambda r: r["index"])
-    cols = [c for c in ("psnr", "ssim", "lpips", "id") if any(c in r for r in rows)]
+    cols = [c for c in COLUMNS if any(c in r for r in rows)]
     return {
         "dataset": dataset, "count": len(rows), "window": window,
-        "psnr_infinite": sum(1 for r in rows if r.get("psnr") is None),
+        "psnr_infinite": sum(1 for r in rows if "sse" in r and r.get("psnr") is None),
         "mean": {c: _mean([r.get(c) for r in rows]) for c in cols},
         "images": rows,
     }
@@ -87,28 +89,49 @@ class Evaluator:
 
     `names`: one `(lq, hq)` pair of file names per image (or None).  `lpips` / `idloss` add the columns `lpips`
     (= PerceptualLoss(restored, gt) per image) and `id` (= cosine of the IDLoss.get_id embeddings per image); both see the
-    de-quantised uint8 images, so every column describes the files on disk."""
+    de-quantised uint8 images, so every column describes the files on disk.
 
-    def __init__(self, window="gauss11", lpips=None, idloss=None):
+    `niqe` = (mu, cov) of a pristine model (`niqe.load_params`) adds the column `niqe`: the no-reference score of the restored image
+    alone (one more launch per batch; the 36 x 36 finish runs on the host inside `report()`; an image without two usable blocks gets
+    None).  With `niqe` and neither `lpips` nor `idloss`, `add(restored, None, names)` scores a batch that has no ground truth: its
+    rows hold `niqe` only."""
+
+    def __init__(self, window="gauss11", lpips=None, idloss=None, niqe=None, niqe_crop_border=0):
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {WINDOWS} (got {window!r})")
-        self.window, self.lpips, self.idloss = window, lpips, idloss
-        self.meta = []       # (index, lq, hq, samples per image)
+        self.window, self.lpips, self.idloss, self.niqe, self.niqe_crop_border = window, lpips, idloss, niqe, niqe_crop_border
+        self.meta = []       # (index, lq, hq, samples per image; None without ground truth)
         self.dev = {"sse": [], "ssim": [], "lpips": [], "id": []}
+        self.niqe_feats = []  # per batch (B, nblk, 36) float64 on the device
 
     def __len__(self):
         return len(self.meta)
 
     def add(self, restored, gt, names=None, indices=None):
         from . import hip_ops as H
-        if restored.dtype != torch.uint8 or gt.dtype != torch.uint8:
+        if gt is None:
+            if self.niqe is None or self.lpips is not None or self.idloss is not None:
+                raise RuntimeError("Evaluator.add without ground truth needs an Evaluator that scores NIQE only (niqe=params, no lpips / idloss)")
+            if self.dev["sse"]:
+                raise RuntimeError("Evaluator.add: this evaluator already holds batches with ground truth")
+        if not isinstance(restored, torch.Tensor) or restored.dtype != torch.uint8 or (gt is not None and gt.dtype != torch.uint8):
             raise RuntimeError("Evaluator.add takes the (B, H, W, 3) uint8 tensors that go to disk (hip_ops.quantize_u8_nhwc)")
-        restored, gt = _as_u8_pair(restored, gt)
+        if gt is None:
+            restored, _ = _as_u8_pair(restored, restored)
+        else:
+            if self.meta and not self.dev["sse"]:
+                raise RuntimeError("Evaluator.add: this evaluator already holds batches without ground truth")
+            restored, gt = _as_u8_pair(restored, gt)
         B = restored.shape[0]
         names = [(None, None)] * B if names is None else [tuple(n) for n in names]
         indices = list(range(len(self.meta), len(self.meta) + B)) if indices is None else [int(i) for i in indices]
         if len(names) != B or len(indices) != B or any(len(n) != 2 for n in names):
             raise RuntimeError(f"Evaluator.add: {B} images need {B} (lq, hq) name pairs and indices")
+        if self.niqe is not None:
+            self.niqe_feats.append(H.niqe_features_u8(restored, self.niqe_crop_border)[0])
+        if gt is None:
+            self.meta.extend((i, n[0], n[1], None) for i, n in zip(indices, names))
+            return
         sse, ssim = H.pair_stats_u8(restored, gt, self.window)
         self.dev["sse"].append(sse)
         self.dev["ssim"].append(ssim)
@@ -126,15 +149,30 @@ class Evaluator:
     def report(self, dataset=None):
         cols = [k for k, v in self.dev.items() if v]
         # one copy, one synchronisation: every column as float64 (an sse is an integer below 2^53, so it survives exactly)
-        table = torch.stack([torch.cat(self.dev[k]).to(torch.float64) for k in cols]).cpu().tolist() if self.meta else []
-        host = dict(zip(cols, table))
+        table = torch.stack([torch.cat(self.dev[k]).to(torch.float64) for k in cols]).cpu().tolist() if self.meta and cols else []
+        host = dict(zip(cols, table)) if cols else {}
+        scores = None
+        if self.niqe is not None and self.meta:
+            from .niqe import score_from_features
+            # one more copy: the block features of every image, flattened (batches of different sizes have different block counts)
+            flat = torch.cat([f.reshape(-1) for f in self.niqe_feats]).cpu().numpy()
+            scores, at = [], 0
+            for f in self.niqe_feats:
+                per = f.shape[1] * f.shape[2]
+                for _ in range(f.shape[0]):
+                    scores.append(score_from_features(flat[at:at + per].reshape(f.shape[1], f.shape[2]), self.niqe))
+                    at += per
         rows = []
         for k, (index, lq, hq, count) in enumerate(self.meta):
-            sse = int(host["sse"][k])
-            row = {"index": index, "lq": lq, "hq": hq, "sse": sse, "psnr": psnr_from_sse(sse, count), "ssim": host["ssim"][k]}
+            row = {"index": index, "lq": lq, "hq": hq}
+            if count is not None:
+                sse = int(host["sse"][k])
+                row.update({"sse": sse, "psnr": psnr_from_sse(sse, count), "ssim": host["ssim"][k]})
             for col in ("lpips", "id"):
                 if col in host:
                     row[col] = host[col][k]
+            if scores is not None:
+                row["niqe"] = scores[k]
             rows.append(row)
         return summarize(rows, dataset, self.window)
 
@@ -164,7 +202,7 @@ def merge_reports(paths):
 
 def summary_line(report):
     m = report["mean"]
-    parts = [f"{c} {m[c]:.6g}" if m.get(c) is not None else f"{c} n/a" for c in ("psnr", "ssim", "lpips", "id") if c in m]
+    parts = [f"{c} {m[c]:.6g}" if m.get(c) is not None else f"{c} n/a" for c in COLUMNS if c in m]
     return "metrics %s (%s, %d images, %d identical): %s" % (report["dataset"], report["window"], report["count"],
                                                             report["psnr_infinite"], ", ".join(parts))
 

@@ -2,6 +2,7 @@
 
     python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
         [--ingest host|device] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
+        [--niqe_params NPZ]
 
 `vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
 puts it under this repository's rule that a feature leaves every existing `*_test.py` / `test_*.py` file as it is.  This module
@@ -11,7 +12,9 @@ tensors of a batch go to `metrics.Evaluator.add` (quantised once, used twice; no
 still overlaps the next batch), and after `writer.drain()` the dataset's `metrics_<rank>.json` is written beside its PNGs and one
 summary line printed.  `--metrics` is off by default: without it the output directory is byte for byte that of
 `vspbfr_amd.restoration_test` (tests/test_metrics_cli_gpu.py compares the two).  `--metrics` with a dataset whose
-`--hq_data_list` entry is `None` is refused before anything is loaded.  Multi-GPU as restoration_test; `metrics.merge_reports`
+`--hq_data_list` entry is `None` is refused before anything is loaded -- unless `--niqe_params NPZ` (a pristine model:
+`vspbfr_amd.niqe_fit`) is given: then every report gains the no-reference `niqe` column of the restored image, and a dataset without
+ground truth gets a report with that column alone.  Multi-GPU as restoration_test; `metrics.merge_reports`
 joins the per-rank files."""
 import argparse
 import os
@@ -58,7 +61,9 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
     evaluator = None
     if args.metrics:
         from .metrics import Evaluator
-        evaluator = Evaluator(args.ssim_window, *args.scorers)
+        niqe_params = getattr(args, "niqe_model", None)
+        # a dataset without ground truth is scored by NIQE alone (main() has refused it already when no model was given)
+        evaluator = Evaluator(args.ssim_window, *args.scorers, niqe=niqe_params) if data.hq is not None else Evaluator(args.ssim_window, niqe=niqe_params)
     print("testing!!! len:%d (rank %d handles %d..%d)" % (len(data), rank, lo, hi))
     with torch.no_grad():
         for idx, low, gts in _batches(args, data, lo, hi, device):
@@ -68,7 +73,10 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
                 if t is not None:
                     u8[kind] = writer.submit(t.to(device) if kind == "gt" else t, [output_name(eval_dict, i, rank, data_name, kind) for i in idx])
             if evaluator is not None:   # the bytes that go to disk, scored on the device: no host synchronisation here
-                evaluator.add(u8["restore"], u8["gt"], [(os.path.relpath(data.lq[i], lq_root), os.path.relpath(data.hq[i], hq_root)) for i in idx], idx)
+                if data.hq is not None:
+                    evaluator.add(u8["restore"], u8["gt"], [(os.path.relpath(data.lq[i], lq_root), os.path.relpath(data.hq[i], hq_root)) for i in idx], idx)
+                else:
+                    evaluator.add(u8["restore"], None, [(os.path.relpath(data.lq[i], lq_root), None) for i in idx], idx)
     writer.drain()
     if evaluator is not None:
         from .metrics import summary_line, write_report
@@ -110,12 +118,24 @@ def main(argv=None):
                     help="extension: SSIM window (gauss11: Wang et al.; uniform7: scikit-image's default, the reference's dssim)")
     ap.add_argument("--lpips_weights", type=str, default=None, help="extension: LIN[,VGG] weight files; adds the lpips column")
     ap.add_argument("--id_weights", type=str, default=None, help="extension: resnet101(256) state dict; adds the id column")
+    ap.add_argument("--niqe_params", type=str, default=None,
+                    help="extension: .npz pristine model (mu_pris_param, cov_pris_param; python -m vspbfr_amd.niqe_fit); adds the no-reference "
+                         "niqe column and lets a dataset without ground truth be scored by it alone")
     args = ap.parse_args(argv)
     if not args.metrics and (args.lpips_weights or args.id_weights):
         ap.error("--lpips_weights / --id_weights only have a meaning with --metrics")
+    if not args.metrics and args.niqe_params:
+        ap.error("--niqe_params only has a meaning with --metrics")
+    args.niqe_model = None
+    if args.niqe_params:
+        from .niqe import load_params
+        try:
+            args.niqe_model = load_params(args.niqe_params)
+        except (ValueError, OSError) as e:
+            ap.error(str(e))
     if args.metrics:
         missing = [d["name"] for d in get_store_data(args.lq_data_list, args.hq_data_list, args.data_name_list) if d["hq"] in ("None", "")]
-        if missing:
+        if missing and args.niqe_model is None:
             ap.error("--metrics needs a ground-truth root (--hq_data_list) for every dataset; none given for: " + ", ".join(missing))
     args.latent, args.n_mlp = 512, 8
     from . import hip_ops

@@ -2,7 +2,10 @@
 `python -m vspbfr_amd.restoration_metrics`): what someone comparing against another method's outputs needs.
 
     python -m vspbfr_amd.score --restored eval_dir/.../demo --gt eval_dir/.../demo [--pattern _restore.png/_gt.png]
-        [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--batch 8] [--out metrics.json]
+        [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--niqe_params NPZ] [--batch 8] [--out metrics.json]
+
+`--niqe_params` (a pristine model, `vspbfr_amd.niqe_fit` or a published one) adds the no-reference `niqe` column and makes --gt
+optional: without --gt every file of --restored that carries the restored suffix (all files when none does) is scored alone.
 
 Pairing: a file `<stem><restored suffix>` of --restored goes with `<stem><gt suffix>` of --gt (the CLI's own naming,
 `{index}_{rank}_{name}_restore.png` / `..._gt.png`); when no file of --restored carries the suffix, the two folders are
@@ -37,35 +40,45 @@ def pair_files(restored_dir, gt_dir, pattern="_restore.png/_gt.png"):
 
 
 def _load_u8(path):
-    import numpy as np
-    import torch
-    from PIL import Image
-    return torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8).copy())
+    from .imageio import load_rgb_u8
+    return load_rgb_u8(path)
 
 
-def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda"):
-    """The report of a list of (restored, gt) files; images of one size are batched, an odd one goes alone."""
+def restored_files(restored_dir, pattern="_restore.png/_gt.png"):
+    """[(restored path, None)] for a run without ground truth -- pure host code"""
+    if pattern.count("/") != 1 or not all(pattern.split("/")):
+        raise ValueError(f"--pattern takes RESTORED_SUFFIX/GT_SUFFIX (got {pattern!r})")
+    files = list_images(restored_dir)
+    tagged = [p for p in files if p.endswith(pattern.split("/")[0])]
+    if not (tagged or files):
+        raise ValueError(f"no images in {restored_dir}")
+    return [(p, None) for p in (tagged or files)]
+
+
+def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda", niqe=None):
+    """The report of a list of (restored, gt) files; images of one size are batched, an odd one goes alone.  gt = None in every
+    pair (with `niqe` params): the no-reference report."""
     import torch
 
     from .metrics import Evaluator
-    ev = Evaluator(window, lpips, idloss)
+    ev = Evaluator(window, lpips, idloss, niqe)
     pend, shape = [], None
 
     def flush():
         if pend:
             r = torch.stack([p[1] for p in pend]).to(device, non_blocking=True)
-            g = torch.stack([p[2] for p in pend]).to(device, non_blocking=True)
+            g = None if pend[0][2] is None else torch.stack([p[2] for p in pend]).to(device, non_blocking=True)
             ev.add(r, g, [p[3] for p in pend], [p[0] for p in pend])
             pend.clear()
 
     for i, (rp, gp) in enumerate(pairs):
-        r, g = _load_u8(rp), _load_u8(gp)
-        if r.shape != g.shape:
+        r, g = _load_u8(rp), None if gp is None else _load_u8(gp)
+        if g is not None and r.shape != g.shape:
             raise ValueError(f"{rp} is {tuple(r.shape[:2])}, {gp} is {tuple(g.shape[:2])}: a pair must have one size")
         if shape != r.shape or len(pend) >= batch:
             flush()
             shape = r.shape
-        pend.append((i, r, g, (os.path.basename(rp), os.path.basename(gp))))
+        pend.append((i, r, g, (os.path.basename(rp), None if gp is None else os.path.basename(gp))))
     flush()
     return ev.report(dataset)
 
@@ -73,24 +86,33 @@ def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, datas
 def main(argv=None):
     ap = argparse.ArgumentParser(description="PSNR / SSIM / LPIPS / ID of a folder of restored PNGs against ground truth (MI355X)")
     ap.add_argument("--restored", required=True)
-    ap.add_argument("--gt", required=True)
+    ap.add_argument("--gt", default=None, help="ground-truth folder; optional with --niqe_params")
     ap.add_argument("--pattern", default="_restore.png/_gt.png", help="RESTORED_SUFFIX/GT_SUFFIX")
     ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11")
     ap.add_argument("--lpips_weights", default=None, help="LIN[,VGG] weight files; adds the lpips column")
     ap.add_argument("--id_weights", default=None, help="resnet101(256) state dict; adds the id column")
+    ap.add_argument("--niqe_params", default=None, help=".npz with mu_pris_param / cov_pris_param; adds the niqe column")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dataset", default=None, help="name written into the report")
     ap.add_argument("--out", default=None, help="write the JSON report here (default: print it)")
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
+    if args.gt is None and not args.niqe_params:
+        ap.error("--gt is required unless --niqe_params asks for the no-reference score")
+    if args.gt is None and (args.lpips_weights or args.id_weights):
+        ap.error("--lpips_weights / --id_weights compare against ground truth: they need --gt")
+    niqe_params = None
     try:
-        pairs = pair_files(args.restored, args.gt, args.pattern)
+        if args.niqe_params:
+            from .niqe import load_params
+            niqe_params = load_params(args.niqe_params)
+        pairs = pair_files(args.restored, args.gt, args.pattern) if args.gt is not None else restored_files(args.restored, args.pattern)
     except (ValueError, FileNotFoundError) as e:
         ap.error(str(e))
     from .metrics import load_scorers, summary_line, write_report
     lp, idl = load_scorers(args.lpips_weights, args.id_weights)
-    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset)
+    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset, niqe=niqe_params)
     if args.out:
         write_report(report, args.out)
     else:
