@@ -40,7 +40,8 @@ const char* vsp_last_error(void);
 /* number of HIP devices visible, or a negative VSP_E* code (used by the loader's self-check). */
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
- * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item): lets a binding in
+ * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
+ * 8 = vsp_face_item, 9 = vsp_face_tile): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -826,6 +827,64 @@ int vsp_png_encode_u8(uint8_t* out, size_t out_capacity, int32_t* seg_bytes, uin
 size_t vsp_niqe_work_bytes(int B, int H, int W, int crop_border);
 int vsp_niqe_features_u8(double* features, double* moments_or_null, float* sharpness, const uint8_t* img, int B, int H, int W,
                          int crop_border, const double* rgam_table, void* work, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Faces inside whole photos (csrc/face_warp.hip): the aligned S x S crop of every face of a ragged batch of packed RGB
+ * photos, and the feathered paste-back of the restored crops into the output photos.  Integer fixed point throughout, so the bytes
+ * equal tests/photo_ref.py.  The host (vspbfr_amd/photo.py) turns a face's float64 2 x 3 matrix M, destination -> source, into
+ * int32 tables for the destination columns x and rows y it covers (rne = round half to even):
+ *     ax[x] = rne(M00 x 1024)   bx[x] = rne(M10 x 1024)   cx[y] = rne((M01 y + M02) 1024) + 16   cy[y] = rne((M11 y + M12) 1024) + 16
+ *     X = (cx[y] + ax[x]) >> 5,  Y = (cy[y] + bx[x]) >> 5        Q5 source coordinates (arithmetic shifts)
+ *     ix = X >> 5, fx = X & 31, iy = Y >> 5, fy = Y & 31
+ *     v  = (sum_{i,j in {0,1}} 32 (i ? fx : 32 - fx)(j ? fy : 32 - fy) p(ix + i, iy + j) + 16384) >> 15     (the weights sum to 2^15)
+ * A face's tables lie at int32 offset tab_off of `tables` as ax[nx], bx[nx], cx[ny], cy[ny].  `tables`, `items`, `tiles`, `tile_faces`
+ * and `ramp` are given twice: in HOST memory, where every entry is checked before anything is launched, and in device memory, which
+ * the kernels read.  VSP_EINVAL, nothing launched: a null pointer, a table entry of magnitude 2^30 or more, an offset outside its
+ * buffer, a size above the limits, a buffer of 2 GiB or more.
+ *
+ * vsp_face_crop_u8   src: the packed photos, face i's (h, w, 3) photo at byte offset src_off, rows of 3 w bytes without padding;
+ *                    M = A^-1 (crop -> photo), nx = ny = S; a tap outside the photo reads the border colour.
+ *                    out_u8 (n, S, S, 3) uint8 and / or out_f32 (n, 3, S, S) fp32 = ((v / 255) - 0.5) / 0.5, three separately rounded
+ *                    operations as vsp_lanczos_resize_u8 writes them; either may be NULL, not both.
+ * vsp_face_paste_u8  in place on `photos`, the packed output photos.  Face i's source is the restored crop at byte offset src_off of
+ *                    `crops` (h = w = S); M = P (output photo -> crop); its tables cover the columns x0 .. x0 + nx - 1 and the rows
+ *                    y0 .. y0 + ny - 1 of its bounding box in the output photo.  One workgroup per tile of VSP_FACE_TILE^2 pixels; the
+ *                    tiles ascend strictly by (photo, y0, x0), so a pixel belongs to one thread.  A pixel walks its tile's faces
+ *                    (tile_faces[face0 .. face0 + nfaces - 1], ascending face indices) in order:
+ *                        d = min(X, Y, (S - 1) 32 - X, (S - 1) 32 - Y);  d < 0: the face does not touch the pixel; otherwise
+ *                        w = ramp[min(d >> 2, ramp_len - 1)],  f = v of the crop with tap indices clamped to S - 1,
+ *                        out = (w f + (256 - w) bg + 128) >> 8,  bg the running result.
+ *                    ramp: uint16 0..256 indexed by the distance from the crop border in 1/8 px, ramp[0] = 0 (else VSP_EINVAL).
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_FACE_TILE 32          /* paste tile side; tile origins are multiples of it */
+#define VSP_FACE_MAX_SIDE 8192    /* crop side S and the extents of one face's tables */
+#define VSP_FACE_MAX_ITEMS 65535  /* faces per launch */
+#define VSP_FACE_MAX_RAMP 65536   /* ramp entries */
+
+typedef struct vsp_face_item {
+  int64_t src_off;   /* crop: byte offset of the face's photo in `src`; paste: byte offset of its restored crop in `crops` */
+  int64_t tab_off;   /* int32 offset of its tables in `tables`: ax[nx], bx[nx], cx[ny], cy[ny] */
+  int32_t h, w;      /* size of the image at src_off (paste: S, S) */
+  int32_t x0, y0;    /* paste: origin of the clipped bounding box in the output photo; crop: 0, 0 */
+  int32_t nx, ny;    /* destination columns and rows the tables cover (crop: S, S) */
+} vsp_face_item;
+
+typedef struct vsp_face_tile {
+  int64_t dst_off;   /* byte offset of the tile's output photo in `photos` */
+  int32_t h, w;      /* size of that photo */
+  int32_t x0, y0;    /* tile origin in the photo, multiples of VSP_FACE_TILE */
+  int32_t face0;     /* first entry of the tile's faces in `tile_faces` */
+  int32_t nfaces;    /* >= 1 */
+} vsp_face_tile;
+
+int vsp_face_crop_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, size_t src_bytes, const int32_t* tables, const int32_t* tables_dev,
+                     size_t table_ints, const vsp_face_item* items, const vsp_face_item* items_dev, int n, int S, int border_r, int border_g,
+                     int border_b, vsp_stream_t stream);
+int vsp_face_paste_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                      const int32_t* tables_dev, size_t table_ints, const vsp_face_item* items, const vsp_face_item* items_dev, int n, int S,
+                      const vsp_face_tile* tiles, const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces,
+                      const int32_t* tile_faces_dev, size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len,
+                      vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

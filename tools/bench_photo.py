@@ -1,0 +1,159 @@
+"""Device time of the whole-photo face kernels (vspbfr_amd/photo.py, csrc/face_warp.hip) against the same job on the host:
+
+  kernels    16 faces from 8 photos of 1024 x 1536 (two per photo, overlapping, turned and scaled), S = 512, at upscale 1 and 2: one
+             vsp_face_crop_u8 call (uint8 + fp32 outputs) and one vsp_face_paste_u8 call, HIP events, median of 30 after a warm-up
+             (the paste runs in place on the same buffer every time: its work does not depend on the bytes); bytes written from the shapes
+  host       the same crops and pastes by tests/photo_ref.py (NumPy, one thread), once; outputs compared with the device's
+  cli        the dataset loop of vspbfr_amd.restore_photos (restore_photos between device synchronisations) over those 8 photos with and
+             without --save_faces, --batch 8 --timesteps 4 --no_sample, random weights, alternating, three each after a warm run
+
+    python tools/bench_photo.py [--out profiles/photo_bench.json] [--skip-cli]
+"""
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import tempfile
+import time
+from argparse import Namespace
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+PIPELINE_STEP_MS = 39.0      # one 8-image pipeline step of the flagship benchmark: what "well under 1 %" is measured against
+
+
+def workload():
+    import photo_ref as R
+    photos = [R.test_photo(1024, 1536, seed=40 + k) for k in range(8)]
+    marks = [[R.landmarks_for(1.4 + 0.1 * k, 9.0 * k - 30.0, (400.0, 600.0)), R.landmarks_for(0.9 + 0.05 * k, 20.0 - 7.0 * k, (620.0, 820.0))]
+             for k in range(8)]
+    return photos, marks
+
+
+def events(fn, n=30, warm=5):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    med = statistics.median(ms)
+    return {"median_ms": round(med, 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4),
+            "percent_of_pipeline_step": round(100.0 * med / PIPELINE_STEP_MS, 3)}
+
+
+def bench_kernels(photos, marks, upscale):
+    import photo_ref as R
+    from vspbfr_amd import photo as P
+    faces = [(k, pts) for k, per in enumerate(marks) for pts in per]
+    plan = P.FacePlan(photos, faces, size=512, upscale=upscale)
+    plan.upload("cuda")
+    rng = np.random.default_rng(1)
+    restored = rng.integers(0, 256, (plan.n, 512, 512, 3), dtype=np.uint8)
+    rdev = torch.from_numpy(restored).cuda()
+    base = plan.background("cuda")
+    base_host = [b.cpu().numpy() for b in plan.split(base)]
+    res = {"faces": plan.n, "tiles": plan.ntiles, "output_photo": list(plan.out_shape[0])}
+    res["crop_u8_f32"] = events(lambda: P.crop_faces(plan, "cuda", u8=True, f32=True))
+    res["crop_u8_f32"]["bytes_written_mb"] = round(plan.n * 512 * 512 * 3 * 5 / 1e6, 2)
+    out = base.clone()
+    res["paste"] = events(lambda: P.paste_faces(plan, rdev, "cuda", out=out))
+    res["paste"]["pixels_in_tiles_m"] = round(plan.ntiles * 1024 / 1e6, 3)
+    # the host's time for the same job, and the same bytes
+    t0 = time.perf_counter()
+    ref_c = [R.crop(photos[k], R.invert(R.similarity(pts)), 512) for k, pts in faces]
+    t1 = time.perf_counter()
+    ref_p = [R.paste(base_host[k], [(restored[i], R.paste_matrix(R.similarity(pts), upscale)) for i, (kk, pts) in enumerate(faces) if kk == k], 512)
+             for k in range(len(photos))]
+    t2 = time.perf_counter()
+    res["host_numpy_one_thread"] = {"crop_ms": round((t1 - t0) * 1000, 1), "paste_ms": round((t2 - t1) * 1000, 1)}
+    u8, _ = P.crop_faces(plan, "cuda")
+    fresh = P.paste_faces(plan, rdev, "cuda", out=base.clone())
+    res["bytes_equal_host"] = bool(np.array_equal(u8.cpu().numpy(), np.stack(ref_c))
+                                   and all(np.array_equal(g.cpu().numpy(), r) for g, r in zip(plan.split(fresh), ref_p)))
+    return res
+
+
+def bench_cli(tmp, photos, marks):
+    from PIL import Image
+    from vspbfr_amd import restore_photos as RP
+    from vspbfr_amd.diffusion import Code_diffuser
+    from vspbfr_amd.e4e import E4e_embedding, Encoder4Editing, Generator
+    from vspbfr_amd.photo import PhotoRestorer
+    from vspbfr_amd.pipeline import RestorationPipeline, load_ddpm
+    from vspbfr_amd.restorenet import Restoration_net
+    torch.manual_seed(0)
+    ck = os.path.join(tmp, "ckpt")
+    os.makedirs(ck)
+    torch.save({"att_mapper": Code_diffuser(timesteps=4).state_dict()}, os.path.join(ck, "code_diffuser.pt"))
+    enc, dec = Encoder4Editing(50, "ir_se", Namespace(input_channel=3, stylegan_size=1024)), Generator(1024, 512, 8)
+    sd = {"encoder." + k: v for k, v in enc.state_dict().items()}
+    sd.update({"decoder." + k: v for k, v in dec.state_dict().items()})
+    torch.save({"state_dict": sd, "latent_avg": torch.zeros(18, 512),
+                "opts": {"encoder_type": "Encoder4Editing", "stylegan_size": 1024, "start_from_latent_avg": True}}, os.path.join(ck, "psp.pt"))
+    del enc, dec, sd
+    root = os.path.join(tmp, "photos")
+    os.makedirs(root)
+    names = [f"{k:02d}.png" for k in range(len(photos))]
+    for n, a in zip(names, photos):
+        Image.fromarray(a).save(os.path.join(root, n))
+    landmarks = {n: m for n, m in zip(names, marks)}
+    device = torch.device("cuda", 0)
+    g_ema = Restoration_net(512, 512, 8).to(device).eval()
+    psp = E4e_embedding(os.path.join(ck, "psp.pt"), out_size=512, size=1024, device=device, use_generator=True)
+    pipe = RestorationPipeline(g_ema, psp, load_ddpm(os.path.join(ck, "code_diffuser.pt"), device=device, timesteps=4), mixing=0.5, with_sample=False)
+    restorer = PhotoRestorer(pipe, 8)
+    times = {False: [], True: []}
+    for rep in range(4):                       # the first of each is the warm run
+        for save in (False, True):
+            args = Namespace(photos=root, out=os.path.join(tmp, f"out_{int(save)}_{rep}"), batch=8, save_faces=save, upscale=1, size=512, inset=8,
+                             feather=48)
+            torch.manual_seed(123)
+            random.seed(123)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            RP.restore_photos(args, restorer, names, landmarks, device)
+            torch.cuda.synchronize()
+            if rep:
+                times[save].append(round(time.perf_counter() - t0, 4))
+    return {"what": "8 photos of 1024 x 1536, 16 faces, --batch 8 --timesteps 4 --no_sample, decode + restore + PNG, alternating",
+            "loop_s": times[False], "loop_save_faces_s": times[True], "loop_median_s": statistics.median(times[False]),
+            "loop_save_faces_median_s": statistics.median(times[True])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--skip-cli", action="store_true")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_photo: no GPU")
+    photos, marks = workload()
+    res = {"what": "16 faces from 8 photos of 1024 x 1536 (w x h), S = 512; HIP events, median of 30", "pipeline_step_ms": PIPELINE_STEP_MS,
+           "cpus_used": len(os.sched_getaffinity(0))}
+    for s in (1, 2):
+        res[f"upscale_{s}"] = bench_kernels(photos, marks, s)
+    if not a.skip_cli:
+        with tempfile.TemporaryDirectory() as d:
+            res["cli"] = bench_cli(d, photos, marks)
+    line = json.dumps(res, indent=1)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -36,6 +36,8 @@ int vsp_struct_size(int which) {
     case 5: return (int)sizeof(vsp_conv_wgrad_params);
     case 6: return (int)sizeof(vsp_degrade_item);
     case 7: return (int)sizeof(vsp_resample_item);
+    case 8: return (int)sizeof(vsp_face_item);
+    case 9: return (int)sizeof(vsp_face_tile);
     default: return -1;
   }
 }

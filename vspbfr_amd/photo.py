@@ -1,0 +1,336 @@
+"""Faces inside whole photos: the host side of csrc/face_warp.hip and the restorer built on it.
+
+    similarity_from_landmarks   five landmarks -> A (2 x 3, photo -> crop): Umeyama's closed-form least-squares similarity onto the
+                                FFHQ 512^2 template; float64, NumPy
+    FacePlan                    one ragged batch of photos and their faces: the int32 coordinate tables of both kernels, the item and
+                                tile tables, the packed photo bytes -- the counterpart of resample.ResamplePlan
+    crop_faces / paste_faces    vsp_face_crop_u8 / vsp_face_paste_u8 on a plan
+    PhotoRestorer               photos + landmarks -> photos with their faces restored by a RestorationPipeline
+
+All device arithmetic is integer: the float64 geometry ends in the tables built here (`face_tables`), which tests/photo_ref.py restates.
+Integer coordinates are pixel centres; there is no half-pixel shift anywhere.
+
+No torch / HIP import at module level: the geometry and the plan are testable without the library."""
+import ctypes as C
+
+import numpy as np
+
+FFHQ512_TEMPLATE = np.array([[192.98138, 239.94708],      # left eye
+                             [318.90277, 240.1936],       # right eye
+                             [256.63416, 314.01935],      # nose
+                             [201.26117, 371.41043],      # left mouth corner
+                             [313.08905, 371.15118]],     # right mouth corner
+                            dtype=np.float64)
+FFHQ512_TEMPLATE.setflags(write=False)
+
+TILE = 32                      # include/vspbfr_hip.h VSP_FACE_TILE
+MAX_SIDE = 8192                # VSP_FACE_MAX_SIDE
+MAX_ITEMS = 65535              # VSP_FACE_MAX_ITEMS
+MAX_RAMP = 65536               # VSP_FACE_MAX_RAMP
+TABLE_LIMIT = 1 << 30          # a table entry of this magnitude is refused (cx + ax must not wrap)
+DEFAULT_BORDER = (128, 128, 128)
+DEFAULT_INSET, DEFAULT_FEATHER = 8, 48     # px; design choices, not measurements
+
+
+class FaceItem(C.Structure):
+    """include/vspbfr_hip.h vsp_face_item"""
+    _fields_ = [("src_off", C.c_int64), ("tab_off", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "x0", "y0", "nx", "ny")]
+
+
+class FaceTile(C.Structure):
+    """include/vspbfr_hip.h vsp_face_tile"""
+    _fields_ = [("dst_off", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "x0", "y0", "face0", "nfaces")]
+
+
+def _where(photo, face):
+    return f"photo {photo!r}, face {face}"
+
+
+def similarity_from_landmarks(pts5, template=FFHQ512_TEMPLATE, size=512, photo="?", face=0):
+    """A (2 x 3 float64, photo -> crop): the least-squares similarity -- rotation, one uniform scale, translation, never a reflection --
+    that takes the five landmarks onto `template` scaled by size / 512 (Umeyama 1991, closed form with the determinant check).
+    ValueError naming the photo and the face for landmarks that are not (5, 2), not finite, or degenerate (variance below 1e-12)."""
+    try:
+        src = np.asarray(pts5, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{_where(photo, face)}: landmarks are not numbers") from None
+    if src.shape != (5, 2):
+        raise ValueError(f"{_where(photo, face)}: landmarks must have shape (5, 2), got {src.shape}")
+    if not np.all(np.isfinite(src)):
+        raise ValueError(f"{_where(photo, face)}: landmarks are not finite")
+    dst = np.asarray(template, dtype=np.float64) * (float(size) / 512.0)
+    ms, md = src.mean(axis=0), dst.mean(axis=0)
+    sc, dc = src - ms, dst - md
+    var = float((sc * sc).sum() / 5.0)
+    if not var >= 1e-12:
+        raise ValueError(f"{_where(photo, face)}: degenerate landmarks (variance {var:.3g})")
+    U, D, Vt = np.linalg.svd(dc.T @ sc / 5.0)
+    sgn = np.ones(2)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:      # the best orthogonal fit would mirror: flip the weaker axis instead
+        sgn[1] = -1.0
+    R = U @ np.diag(sgn) @ Vt
+    scale = float((D * sgn).sum()) / var
+    t = md - scale * (R @ ms)
+    return np.concatenate([scale * R, t[:, None]], axis=1)
+
+
+def invert_affine(A):
+    """closed-form inverse of a 2 x 3 affine map"""
+    a, b, tx, c, d, ty = (float(v) for v in np.asarray(A, dtype=np.float64).reshape(-1))
+    det = a * d - b * c
+    return np.array([[d / det, -b / det, (b * ty - d * tx) / det], [-c / det, a / det, (c * tx - a * ty) / det]], dtype=np.float64)
+
+
+def paste_matrix(A, upscale=1):
+    """P (output photo -> crop): A after the output coordinates are divided by the upscale factor"""
+    P = np.array(A, dtype=np.float64)
+    P[:, :2] = P[:, :2] / float(upscale)
+    return P
+
+
+def face_tables(M, xs, ys, photo="?", face=0):
+    """The int32 tables of one face for M (2 x 3 float64, destination -> source), destination columns xs and rows ys, concatenated as the
+    kernels read them: ax[nx], bx[nx], cx[ny], cy[ny] (include/vspbfr_hip.h).  np.rint rounds half to even."""
+    M = np.asarray(M, dtype=np.float64)
+    xs, ys = np.asarray(xs, dtype=np.float64), np.asarray(ys, dtype=np.float64)
+    parts = (np.rint(M[0, 0] * xs * 1024.0), np.rint(M[1, 0] * xs * 1024.0), np.rint((M[0, 1] * ys + M[0, 2]) * 1024.0) + 16.0,
+             np.rint((M[1, 1] * ys + M[1, 2]) * 1024.0) + 16.0)
+    t = np.concatenate(parts)
+    if t.size and not np.all(np.abs(t) < TABLE_LIMIT):
+        raise ValueError(f"{_where(photo, face)}: the face lies too far outside the photo or is too small (a coordinate table entry reaches 2^30)")
+    return t.astype(np.int32)
+
+
+def face_bbox(P, S, H, W):
+    """(x0, y0, x1, y1), ends exclusive: the corners of the crop square [0, S - 1]^2 taken back through P into the (H, W) output photo,
+    floor / ceil with one pixel of margin (the tables are rounded), clipped to the photo.  Empty (x1 <= x0 or y1 <= y0) where the face
+    lies outside."""
+    Q = invert_affine(P)
+    c = np.array([[0.0, 0.0], [S - 1.0, 0.0], [0.0, S - 1.0], [S - 1.0, S - 1.0]])
+    px = Q[0, 0] * c[:, 0] + Q[0, 1] * c[:, 1] + Q[0, 2]
+    py = Q[1, 0] * c[:, 0] + Q[1, 1] * c[:, 1] + Q[1, 2]
+    x0, x1 = int(np.floor(px.min())) - 1, int(np.ceil(px.max())) + 2
+    y0, y1 = int(np.floor(py.min())) - 1, int(np.ceil(py.max())) + 2
+    return max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+
+
+def default_ramp(inset=DEFAULT_INSET, feather=DEFAULT_FEATHER):
+    """The blend weight over the distance from the crop border in 1/8 px, uint16 0..256: 0 up to `inset` px, a raised cosine up to 256
+    over the next `feather` px; L = 8 (inset + feather) + 1 entries, the last one holds for every larger distance."""
+    inset, feather = int(inset), int(feather)
+    if inset < 0 or feather < 0 or 8 * (inset + feather) + 1 > MAX_RAMP:
+        raise ValueError(f"default_ramp: inset {inset}, feather {feather}")
+    px = np.arange(8 * (inset + feather) + 1, dtype=np.float64) / 8.0
+    t = np.clip((px - inset) / float(feather), 0.0, 1.0) if feather > 0 else (px > inset).astype(np.float64)
+    r = np.rint(128.0 * (1.0 - np.cos(np.pi * t))).astype(np.uint16)
+    r[0] = 0
+    return r
+
+
+class FacePlan:
+    """One ragged batch: `photos` (uint8 (h, w, 3) arrays) and `faces` = [(photo index, five landmarks), ...] in paste order.
+
+    For face i: A_i = similarity_from_landmarks; the crop tables of M = A^-1 over the S x S crop; P = paste_matrix(A, upscale), its
+    bounding box in the (upscale h, upscale w) output photo and the paste tables over that box.  The paste tiles: every 32 x 32 tile of
+    the output photos' tile grids that a box meets, ascending by (photo, row, column), each with its faces in list order.
+    `names` (one per photo) appear in error messages."""
+
+    def __init__(self, photos, faces, size=512, upscale=1, names=None):
+        self.S, self.upscale = int(size), int(upscale)
+        if not 1 <= self.S <= MAX_SIDE or self.upscale < 1:
+            raise ValueError(f"FacePlan: size {size}, upscale {upscale}")
+        if len(faces) > MAX_ITEMS:
+            raise ValueError(f"FacePlan: at most {MAX_ITEMS} faces")
+        names = [str(k) for k in range(len(photos))] if names is None else list(names)
+        self.photos, self.src_off, self.out_off, self.out_shape = [], [], [], []
+        src = out = 0
+        for k, a in enumerate(photos):
+            a = np.asarray(a)
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"photo {names[k]!r}: must be uint8 (h, w, 3), got {a.dtype} {a.shape}")
+            self.photos.append(np.ascontiguousarray(a))
+            self.src_off.append(src)
+            self.out_off.append(out)
+            self.out_shape.append((a.shape[0] * self.upscale, a.shape[1] * self.upscale))
+            src += a.size
+            out += a.size * self.upscale * self.upscale
+        self.src_bytes, self.out_bytes = src, out
+        if max(src, out) >= 1 << 31:
+            raise ValueError("FacePlan: a batch of photos must stay below 2 GiB")
+        S, n = self.S, len(faces)
+        self.n = n
+        self.face_photo, self.A, self.P, self.boxes = [], [], [], []
+        self.crop_items, self.paste_items = (FaceItem * max(n, 1))(), (FaceItem * max(n, 1))()
+        crop_tabs, paste_tabs, ct, pt = [], [], 0, 0
+        per_photo = {}
+        which = {}
+        for i, (k, pts) in enumerate(faces):
+            k = int(k)
+            if not 0 <= k < len(self.photos):
+                raise ValueError(f"face {i}: photo index {k}")
+            j = which[k] = which.get(k, -1) + 1           # the face's number inside its photo, for messages
+            h, w = self.photos[k].shape[:2]
+            A = similarity_from_landmarks(pts, size=S, photo=names[k], face=j)
+            P = paste_matrix(A, self.upscale)
+            oh, ow = self.out_shape[k]
+            x0, y0, x1, y1 = face_bbox(P, S, oh, ow)
+            if x1 <= x0 or y1 <= y0:
+                x0 = y0 = x1 = y1 = 0
+            self.face_photo.append(k)
+            self.A.append(A)
+            self.P.append(P)
+            self.boxes.append((x0, y0, x1, y1))
+            t = face_tables(invert_affine(A), np.arange(S), np.arange(S), names[k], j)
+            it = self.crop_items[i]
+            it.src_off, it.tab_off, it.h, it.w, it.x0, it.y0, it.nx, it.ny = self.src_off[k], ct, h, w, 0, 0, S, S
+            crop_tabs.append(t)
+            ct += t.size
+            t = face_tables(P, np.arange(x0, x1), np.arange(y0, y1), names[k], j)
+            it = self.paste_items[i]
+            it.src_off, it.tab_off, it.h, it.w, it.x0, it.y0, it.nx, it.ny = i * 3 * S * S, pt, S, S, x0, y0, x1 - x0, y1 - y0
+            paste_tabs.append(t)
+            pt += t.size
+            if x1 > x0:
+                per_photo.setdefault(k, []).append(i)
+        self.crop_tables = np.concatenate(crop_tabs) if crop_tabs else np.zeros(0, dtype=np.int32)
+        self.paste_tables = np.concatenate(paste_tabs) if paste_tabs else np.zeros(0, dtype=np.int32)
+        tiles, tile_faces = [], []
+        for k in sorted(per_photo):
+            oh, ow = self.out_shape[k]
+            cover = {}
+            for i in per_photo[k]:                         # ascending face index: list order
+                x0, y0, x1, y1 = self.boxes[i]
+                for ty in range(y0 // TILE, (y1 - 1) // TILE + 1):
+                    for tx in range(x0 // TILE, (x1 - 1) // TILE + 1):
+                        cover.setdefault((ty, tx), []).append(i)
+            for (ty, tx) in sorted(cover):
+                tiles.append((self.out_off[k], oh, ow, tx * TILE, ty * TILE, len(tile_faces), len(cover[(ty, tx)])))
+                tile_faces.extend(cover[(ty, tx)])
+        self.ntiles = len(tiles)
+        self.tiles = (FaceTile * max(self.ntiles, 1))()
+        for t, v in zip(self.tiles, tiles):
+            t.dst_off, t.h, t.w, t.x0, t.y0, t.face0, t.nfaces = v
+        self.tile_faces = np.asarray(tile_faces, dtype=np.int32)
+        self._host = self._dev = None
+        self._ramps = {}
+
+    # ---------------------------------------------------------------------------------------------------------------- device side
+    def pack(self):
+        """every table and the photo bytes in ONE pinned uint8 buffer, 16-byte aligned sections (the photos packed without padding)
+        -> (buffer, {section: (offset, bytes)})"""
+        import torch
+        if self._host is None:
+            n, nt = self.n, self.ntiles
+            parts = [("crop_items", np.frombuffer(bytes(self.crop_items), dtype=np.uint8)[:n * C.sizeof(FaceItem)]),
+                     ("paste_items", np.frombuffer(bytes(self.paste_items), dtype=np.uint8)[:n * C.sizeof(FaceItem)]),
+                     ("tiles", np.frombuffer(bytes(self.tiles), dtype=np.uint8)[:nt * C.sizeof(FaceTile)]),
+                     ("tile_faces", self.tile_faces.view(np.uint8)), ("crop_tables", self.crop_tables.view(np.uint8)),
+                     ("paste_tables", self.paste_tables.view(np.uint8))]
+            sections, off = {}, 0
+            for name, a in parts:
+                sections[name] = (off, a.size)
+                off = (off + a.size + 15) // 16 * 16
+            sections["photos"] = (off, self.src_bytes)
+            host = torch.empty(off + self.src_bytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+            hv = host.numpy()
+            for name, a in parts:
+                hv[sections[name][0]:sections[name][0] + a.size] = a
+            for o, a in zip(self.src_off, self.photos):
+                hv[off + o:off + o + a.size] = a.reshape(-1)
+            self._host = (host, sections)
+        return self._host
+
+    def upload(self, device):
+        """one copy on the current stream -> {section: device uint8 view}; kept for the later calls on the same device"""
+        import torch
+        device = torch.device(device)
+        if self._dev is None or self._dev[0] != device:
+            host, sections = self.pack()
+            dev = host.to(device, non_blocking=True)
+            self._dev = (device, {name: dev[o:o + nb] for name, (o, nb) in sections.items()})
+        return self._dev[1]
+
+    def background(self, device):
+        """The packed output photos before any face is pasted, a fresh device uint8 buffer of out_bytes: the photos themselves at upscale
+        1, else each photo resized to exactly (upscale w, upscale h) -- by the device LANCZOS kernel where resample.kernel_serves takes
+        it, by PIL otherwise; both are Pillow's bytes."""
+        import torch
+        dev = self.upload(device)
+        if self.upscale == 1:
+            return dev["photos"].clone()
+        from .resample import ResamplePlan, host_resize, kernel_serves
+        out = torch.empty(self.out_bytes, dtype=torch.uint8, device=device)
+        for a, o, (oh, ow) in zip(self.photos, self.out_off, self.out_shape):
+            h, w = a.shape[:2]
+            if kernel_serves(w, h, ow, oh, (0, 0, ow, oh), (oh, ow)):
+                u8, _ = ResamplePlan([a], [(ow, oh)], [(0, 0)], (oh, ow)).run(device, u8=True, f32=False)
+                out[o:o + 3 * oh * ow] = u8.reshape(-1)
+            else:
+                out[o:o + 3 * oh * ow] = torch.from_numpy(host_resize(a, ow, oh, (0, 0, ow, oh)).reshape(-1).copy()).to(device)
+        return out
+
+    def split(self, packed):
+        """the (upscale h, upscale w, 3) views of a packed output buffer, one per photo"""
+        return [packed[o:o + 3 * oh * ow].view(oh, ow, 3) for o, (oh, ow) in zip(self.out_off, self.out_shape)]
+
+
+def crop_faces(plan, device, u8=True, f32=False, border=DEFAULT_BORDER):
+    """The aligned crops of every face of the plan on `device`, current stream -> (u8 (F, S, S, 3) or None, f32 (F, 3, S, S) or None)."""
+    from . import hip_ops
+    dev = plan.upload(device)
+    return hip_ops.face_crop_u8(plan, dev["crop_items"], dev["crop_tables"], dev["photos"], border=border, u8=u8, f32=f32)
+
+
+def paste_faces(plan, restored_u8, device, ramp=None, out=None):
+    """Paste the restored crops ((F, S, S, 3) uint8 on the device) into the output photos, in place on `out` (a packed device buffer of
+    plan.out_bytes; default plan.background(device)) -> out.  ramp: uint16 weights 0..256 over the distance from the crop border in
+    1/8 px, ramp[0] = 0; default default_ramp().  plan.split(out) gives the photos."""
+    import torch
+
+    from . import hip_ops
+    dev = plan.upload(device)
+    if out is None:
+        out = plan.background(device)
+    ramp = default_ramp() if ramp is None else np.ascontiguousarray(np.asarray(ramp))
+    if ramp.dtype != np.uint16 or ramp.ndim != 1:
+        raise ValueError("paste_faces: ramp must be a one-dimensional uint16 array")
+    key = (str(torch.device(device)), ramp.tobytes())
+    ramp_dev = plan._ramps.get(key)              # a plan pasted more than once uploads its ramp once
+    if ramp_dev is None:
+        ramp_dev = plan._ramps[key] = torch.from_numpy(ramp.view(np.int16).copy()).to(device)
+    hip_ops.face_paste_u8(plan, out, restored_u8, dev["paste_items"], dev["paste_tables"], dev["tiles"], dev["tile_faces"], ramp, ramp_dev)
+    return out
+
+
+class PhotoRestorer:
+    """photos + five-point landmarks -> the photos with every face restored.  The photos stay on the device: crop (vsp_face_crop_u8),
+    `pipe` (a RestorationPipeline) over the faces of all photos in batches of `batch`, quantisation to uint8 as PngWriter does
+    (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4."""
+
+    def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER):
+        if int(upscale) not in (1, 2, 4) or int(batch) < 1:
+            raise ValueError(f"PhotoRestorer: batch {batch}, upscale {upscale}")
+        self.pipe, self.batch, self.upscale, self.size, self.border = pipe, int(batch), int(upscale), int(size), tuple(border)
+        self.ramp = default_ramp(inset, feather)
+
+    def __call__(self, photos, landmarks, device, names=None):
+        """photos: uint8 (h, w, 3) arrays; landmarks: per photo a list of (5, 2) point sets (None or [] for none) ->
+        (output photos: device uint8 (upscale h, upscale w, 3) tensors, crops (F, S, S, 3) uint8, restored (F, S, S, 3) uint8, plan)"""
+        import torch
+
+        from . import hip_ops
+        faces = [(k, pts) for k, per in enumerate(landmarks) for pts in (per or [])]
+        plan = FacePlan(photos, faces, self.size, self.upscale, names)
+        S = self.size
+        if plan.n == 0:
+            empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)
+            return plan.split(plan.background(device)), empty, empty, plan
+        crops, low = crop_faces(plan, device, u8=True, f32=True, border=self.border)
+        restored = []
+        with torch.no_grad():
+            for i in range(0, plan.n, self.batch):
+                out = self.pipe(low[i:i + self.batch])
+                restored.append(hip_ops.quantize_u8_nhwc(out["restored"].contiguous(), -1.0, 1.0))
+        restored = torch.cat(restored) if len(restored) > 1 else restored[0]
+        out = paste_faces(plan, restored, device, self.ramp)
+        return plan.split(out), crops, restored, plan

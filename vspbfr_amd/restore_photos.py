@@ -1,0 +1,162 @@
+"""Restore the faces inside whole photos and give the photos back.
+
+    python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
+        [--inset PX] [--feather PX] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
+
+`vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
+detector: FILE.json maps a photo's path relative to DIR to its faces, each five (x, y) landmarks in photo pixels (pixel centres) --
+left eye, right eye, nose, left and right mouth corner:
+
+    {"relative/name.png": [[[x, y], [x, y], [x, y], [x, y], [x, y]], ...one entry per face], ...}
+
+Per face: the least-squares similarity onto the FFHQ template, an aligned crop on the device, the restoration pipeline (faces of
+several photos share a batch), quantisation to 8 bits as the other CLIs' PNG writer does, and a feathered paste-back in list order
+(vspbfr_amd.photo, csrc/face_warp.hip).  With --upscale 2 or 4 the photo is first resized by Pillow's LANCZOS filter and the
+faces are pasted at that scale.  Output: OUT/<relative stem>.png for every photo -- one without an entry or with no face is written
+through (resized if asked) -- with --save_faces also <stem>_<k>_crop.png and <stem>_<k>_restore.png per face, and report.json
+(report_<rank>.json in a multi-GPU run) listing every photo with its face count.
+
+Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
+contiguous shard of the sorted photo list, no collective."""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from .e4e import E4e_embedding
+from .imageio import PngWriter, list_images
+from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, similarity_from_landmarks
+from .pipeline import RestorationPipeline, load_ddpm, shard_range
+from .restorenet import Restoration_net
+
+MAX_PHOTOS_PER_CALL = 8      # photos decoded and kept on the device together while their faces fill a batch
+
+
+def load_landmarks(path, names):
+    """FILE.json -> {relative name: [(5, 2) float64, ...]}; every face is validated here (ValueError names the photo and the face), an
+    entry for a photo that is not in the list is an error too"""
+    with open(path) as f:
+        raw = json.load(f)
+    if not isinstance(raw, dict):
+        raise ValueError(f"{path}: expected an object that maps photo names to lists of faces")
+    unknown = sorted(set(raw) - set(names))
+    if unknown:
+        raise ValueError(f"{path}: no such photo under --photos: {', '.join(unknown[:5])}")
+    out = {}
+    for name, faces in raw.items():
+        if not isinstance(faces, list):
+            raise ValueError(f"photo {name!r}: expected a list of faces")
+        for k, pts in enumerate(faces):
+            similarity_from_landmarks(pts, photo=name, face=k)
+        out[name] = [np.asarray(p, dtype=np.float64) for p in faces]
+    return out
+
+
+def _decode(path):
+    from PIL import Image
+    return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
+
+
+def _groups(names, landmarks, batch):
+    """consecutive photos whose faces fill at least one batch, at most MAX_PHOTOS_PER_CALL of them"""
+    group, nfaces = [], 0
+    for n in names:
+        group.append(n)
+        nfaces += len(landmarks.get(n, ()))
+        if nfaces >= batch or len(group) == MAX_PHOTOS_PER_CALL:
+            yield group
+            group, nfaces = [], 0
+    if group:
+        yield group
+
+
+def list_photos(root):
+    """the photos under `root` as sorted paths relative to it"""
+    return [os.path.relpath(p, root) for p in list_images(root)]
+
+
+def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
+    lo, hi = shard_range(len(names), rank, world)
+    os.makedirs(args.out, exist_ok=True)
+    writer = PngWriter()
+    report = []
+    print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
+    for group in _groups(names[lo:hi], landmarks, args.batch):
+        photos = [_decode(os.path.join(args.photos, n)) for n in group]
+        outs, crops, restored, plan = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
+        for k, n in enumerate(group):
+            stem = os.path.join(args.out, os.path.splitext(n)[0])
+            os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
+            writer.submit(outs[k][None], [stem + ".png"])
+            mine = [i for i, kk in enumerate(plan.face_photo) if kk == k]
+            if args.save_faces:
+                for j, i in enumerate(mine):
+                    writer.submit(crops[i:i + 1], [f"{stem}_{j}_crop.png"])
+                    writer.submit(restored[i:i + 1], [f"{stem}_{j}_restore.png"])
+            report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ".png", args.out),
+                           "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
+    writer.drain()
+    name = "report.json" if world == 1 else "report_%d.json" % rank
+    with open(os.path.join(args.out, name), "w") as f:
+        json.dump({"upscale": args.upscale, "crop_size": args.size, "inset": args.inset, "feather": args.feather, "photos": report}, f, indent=1)
+    return report
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Restore the faces inside whole photos (MI355X path)")
+    ap.add_argument("--batch", type=int, default=1, help="faces per pipeline batch; faces of several photos share a batch")
+    ap.add_argument("--size", type=int, default=512, help="image sizes for the models: the side of the aligned crop")
+    ap.add_argument("--mixing", type=float, default=0.5, help="probability of latent code mixing")
+    ap.add_argument("--channel_multiplier", type=int, default=2)
+    ap.add_argument("--ckpt", type=str, default=None)
+    ap.add_argument("--ddpm_ckpt", type=str, default="pre-train/code_diffuser.pt")
+    ap.add_argument("--psp_checkpoint_path", type=str, default="pre-train/style_encoder_decoder.pt")
+    ap.add_argument("--timesteps", type=int, default=4, help="DDPM steps")
+    ap.add_argument("--no_sample", action="store_true", help="skip the 1024^2 style-sample tail of the pipeline (it is not written here)")
+    ap.add_argument("--conv_dtype", choices=["f32", "bf16", "bf16x3"], default="f32",
+                    help="bf16 = the bf16-kernel configuration (vsp_conv2d_bf16; not the parity path); "
+                         "bf16x3 = split-precision operands on the bf16 pipe (fp32-grade)")
+    ap.add_argument("--photos", type=str, required=True, help="directory of photos (searched recursively)")
+    ap.add_argument("--landmarks", type=str, required=True, help='JSON: {"relative/name.png": [[[x, y] x 5], ...one entry per face]}')
+    ap.add_argument("--out", type=str, required=True, help="output directory")
+    ap.add_argument("--upscale", type=int, choices=[1, 2, 4], default=1, help="resize the photo (Pillow LANCZOS) and paste the faces at that scale")
+    ap.add_argument("--save_faces", action="store_true", help="also write <stem>_<k>_crop.png and <stem>_<k>_restore.png")
+    ap.add_argument("--inset", type=int, default=DEFAULT_INSET, help="px of the crop border that keep the photo")
+    ap.add_argument("--feather", type=int, default=DEFAULT_FEATHER, help="px over which the blend rises to the restored face")
+    args = ap.parse_args(argv)
+    if args.batch < 1 or args.inset < 0 or args.feather < 0:
+        ap.error("--batch must be at least 1, --inset and --feather at least 0")
+    args.latent, args.n_mlp = 512, 8
+    try:                       # the inputs are checked before any model is loaded
+        names = list_photos(args.photos)
+        landmarks = load_landmarks(args.landmarks, names)
+    except (ValueError, OSError) as e:
+        ap.error(str(e))
+    from . import hip_ops
+    hip_ops.BF16_CONV = {"f32": False, "bf16": True, "bf16x3": "x3"}[args.conv_dtype]
+
+    world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+
+    g_ema = Restoration_net(args.size, args.latent, args.n_mlp, channel_multiplier=args.channel_multiplier)
+    if args.ckpt is not None:
+        print("load models:", args.ckpt)
+        try:
+            g_ema.load_state_dict(torch.load(args.ckpt, map_location="cpu")["g_ema"])
+        except RuntimeError as e:  # as the other CLIs: print and carry on with the initial weights
+            print(str(e))
+    g_ema = g_ema.to(device).eval()
+    psp = E4e_embedding(args.psp_checkpoint_path, out_size=args.size, size=1024, device=device, use_generator=True)
+    diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
+    pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)
+    restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather)
+    restore_photos(args, restorer, names, landmarks, device, rank, world)
+
+
+if __name__ == "__main__":
+    main()
