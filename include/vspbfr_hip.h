@@ -41,7 +41,7 @@ const char* vsp_last_error(void);
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
- * 8 = vsp_face_item, 9 = vsp_face_tile): lets a binding in
+ * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -885,6 +885,52 @@ int vsp_face_paste_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops,
                       const vsp_face_tile* tiles, const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces,
                       const int32_t* tile_faces_dev, size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len,
                       vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Anti-aliased face crop and paste-back (csrc/face_warp.hip; bytes equal tests/photo_aa_ref.py).  Supersets of the two
+ * entries above: an item with reach == 0 is resampled by the four bilinear taps exactly as there, an item with reach > 0 by a tent
+ * filter one DESTINATION pixel wide along the destination's axes, evaluated at source lattice points.  For F (2 x 3, source ->
+ * destination; crop: A, paste: P^-1) the host builds forward tables over the source columns qx = sx0 .. sx0 + snx - 1 and rows
+ * qy = sy0 .. sy0 + sny - 1 (the range may start below 0 and end past the image), at int32 offset fwd_off of `fwd` as fu[snx],
+ * fv[snx], gu[sny], gv[sny]:
+ *     fu[qx] = rne(F00 qx 1024)   fv[qx] = rne(F10 qx 1024)   gu[qy] = rne((F01 qy + F02) 1024)   gv[qy] = rne((F11 qy + F12) 1024)
+ *     U = fu[qx] + gu[qy], V = fv[qx] + gv[qy];  for the destination pixel (x, y) in absolute destination coordinates
+ *     tu = max(0, 1024 - |U - 1024 x|), tv = max(0, 1024 - |V - 1024 y|), w = (tu tv) >> 8
+ *     v_c = (sum w p_c(qx, qy) + (W >> 1)) / W,  W = sum w   (floor division)
+ * summed over the window qx = ix - reach .. ix + reach + 1, qy = iy - reach .. iy + reach + 1 around the centre cell (ix, iy) = (X >> 5,
+ * Y >> 5) of the destination -> source tables; with reach = ceil(|M00| + |M01| + 0.125), M = F^-1, every tap outside the window has
+ * weight 0.  Crop: a point outside the photo reads the border colour; paste: the pixel at the index clamped to 0 .. S - 1.
+ * Checked on the host before anything is launched, beyond what the entries above check: reach < 0 is VSP_EINVAL and reach >
+ * VSP_FACE_AA_MAX_REACH (a minification above 16) VSP_ENOTSUP; for reach > 0 the forward tables lie inside `fwd` with every entry
+ * below 2^30 in magnitude, the destination stays below 2^20 pixels a side, and the source range contains the window of every pixel the
+ * item serves.  That last check takes the extremes of the centre tables: every centre column lies between (min cx + min ax) >> 10 and
+ * (max cx + max ax) >> 10 (rows: cy, bx), and the range must hold those - reach .. + reach + 1.  `fwd` / `fwd_dev` may be NULL when no
+ * item has reach > 0.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_FACE_AA_MAX_REACH 23         /* ceil(16 sqrt(2) + 0.125): a minification of 16 at any turn */
+#define VSP_FACE_AA_MAX_RANGE (1 << 18)  /* source columns / rows one item's forward tables may cover */
+
+typedef struct vsp_face_aa_item {
+  int64_t src_off;   /* as vsp_face_item */
+  int64_t tab_off;
+  int64_t fwd_off;   /* int32 offset of the forward tables in `fwd`: fu[snx], fv[snx], gu[sny], gv[sny] */
+  int32_t h, w;
+  int32_t x0, y0;
+  int32_t nx, ny;
+  int32_t sx0, sy0;  /* first source column / row the forward tables cover (may be negative) */
+  int32_t snx, sny;  /* columns / rows they cover (0 with reach == 0) */
+  int32_t reach;     /* 0: four-tap bilinear; 1 .. VSP_FACE_AA_MAX_REACH: the filter over a (2 reach + 2)^2 window */
+  int32_t pad_;
+} vsp_face_aa_item;
+
+int vsp_face_crop_aa_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, size_t src_bytes, const int32_t* tables, const int32_t* tables_dev,
+                        size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints, const vsp_face_aa_item* items,
+                        const vsp_face_aa_item* items_dev, int n, int S, int border_r, int border_g, int border_b, vsp_stream_t stream);
+int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                         const int32_t* tables_dev, size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints,
+                         const vsp_face_aa_item* items, const vsp_face_aa_item* items_dev, int n, int S, const vsp_face_tile* tiles,
+                         const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
+                         size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

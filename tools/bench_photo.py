@@ -8,6 +8,14 @@
              without --save_faces, --batch 8 --timesteps 4 --no_sample, random weights, alternating, three each after a warm run
 
     python tools/bench_photo.py [--out profiles/photo_bench.json] [--skip-cli]
+
+  --antialias   instead: the anti-aliased kernels (vsp_face_crop_aa_u8 / vsp_face_paste_aa_u8) against the bilinear ones on the
+             same faces -- 16 faces from 8 photos at the same turns, with faces of 256, 1024 and 2048 px (crop minification 0.5 / 2 / 4,
+             paste minification 2 / 0.5 / 0.25; the photos grow to 2560 x 3072 for the 2048 px faces), S = 512, upscale 1.  Per size:
+             both crops and both pastes, median of 30, the ratio filtered / bilinear and the share of one pipeline step; the first
+             face's crop and the first photo's paste are compared with tests/photo_aa_ref.py on the host.
+
+    python tools/bench_photo.py --antialias [--out profiles/photo_aa_bench.json]
 """
 import argparse
 import json
@@ -86,6 +94,49 @@ def bench_kernels(photos, marks, upscale):
     return res
 
 
+def workload_aa(face_px):
+    import photo_ref as R
+    w, h = (1024, 1536) if face_px <= 1024 else (2560, 3072)
+    scale = 512.0 / face_px
+    photos = [R.test_photo(w, h, seed=40 + k) for k in range(8)]
+    marks = [[R.landmarks_for(scale, 9.0 * k - 30.0, (0.39 * w, 0.39 * h)), R.landmarks_for(scale, 20.0 - 7.0 * k, (0.6 * w, 0.53 * h))]
+             for k in range(8)]
+    return photos, marks
+
+
+def bench_antialias(face_px):
+    import photo_aa_ref as AA
+    import photo_ref as R
+    from vspbfr_amd import photo as P
+    photos, marks = workload_aa(face_px)
+    faces = [(k, pts) for k, per in enumerate(marks) for pts in per]
+    plans = {"bilinear": P.FacePlan(photos, faces, size=512), "filtered": P.FacePlan(photos, faces, size=512, antialias=True)}
+    aa = plans["filtered"]
+    rng = np.random.default_rng(1)
+    restored = rng.integers(0, 256, (aa.n, 512, 512, 3), dtype=np.uint8)
+    rdev = torch.from_numpy(restored).cuda()
+    res = {"face_px": face_px, "photo": [photos[0].shape[1], photos[0].shape[0]], "faces": aa.n, "tiles": aa.ntiles,
+           "crop_minify": round(aa.crop_minify[0], 4), "paste_minify": round(aa.paste_minify[0], 4),
+           "crop_reach": sorted({aa.crop_aa_items[i].reach for i in range(aa.n)}),
+           "paste_reach": sorted({aa.paste_aa_items[i].reach for i in range(aa.n)})}
+    for name, plan in plans.items():
+        plan.upload("cuda")
+        out = plan.background("cuda")
+        res[f"crop_{name}"] = events(lambda: P.crop_faces(plan, "cuda", u8=True, f32=True))
+        res[f"paste_{name}"] = events(lambda: P.paste_faces(plan, rdev, "cuda", out=out))
+    for k in ("crop", "paste"):
+        res[f"{k}_ratio_filtered_over_bilinear"] = round(res[f"{k}_filtered"]["median_ms"] / res[f"{k}_bilinear"]["median_ms"], 2)
+    u8, _ = P.crop_faces(aa, "cuda")
+    k0, pts0 = faces[0]
+    ok = np.array_equal(u8[0].cpu().numpy(), AA.crop(photos[k0], R.similarity(pts0), 512))
+    base = aa.background("cuda")
+    fresh = P.paste_faces(aa, rdev, "cuda", out=base.clone())
+    mine = [(restored[i], R.similarity(pts)) for i, (kk, pts) in enumerate(faces) if kk == 0]
+    ok = ok and np.array_equal(aa.split(fresh)[0].cpu().numpy(), AA.paste(photos[0], mine, 512))
+    res["bytes_equal_host_first_face_and_photo"] = bool(ok)
+    return res
+
+
 def bench_cli(tmp, photos, marks):
     from PIL import Image
     from vspbfr_amd import restore_photos as RP
@@ -137,9 +188,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-cli", action="store_true")
+    ap.add_argument("--antialias", action="store_true", help="the anti-aliased kernels against the bilinear ones at three face sizes")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_photo: no GPU")
+    if a.antialias:
+        res = {"what": "16 faces from 8 photos, S = 512, upscale 1: filtered (DESIGN 16) against bilinear kernels; HIP events, median of 30",
+               "pipeline_step_ms": PIPELINE_STEP_MS, "cpus_used": len(os.sched_getaffinity(0)),
+               "sizes": [bench_antialias(px) for px in (256, 1024, 2048)]}
+        line = json.dumps(res, indent=1)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     photos, marks = workload()
     res = {"what": "16 faces from 8 photos of 1024 x 1536 (w x h), S = 512; HIP events, median of 30", "pipeline_step_ms": PIPELINE_STEP_MS,
            "cpus_used": len(os.sched_getaffinity(0))}

@@ -12,7 +12,7 @@ import os
 # allocations.  Loading this library first would pull /opt/rocm's runtime in and leave two HIP runtimes in one process.
 import torch  # noqa: F401
 
-from .photo import FaceItem, FaceTile  # vsp_face_item / vsp_face_tile: the same arrangement for the whole-photo face path
+from .photo import FaceAAItem, FaceItem, FaceTile  # vsp_face_item / vsp_face_tile / vsp_face_aa_item: the same arrangement for the whole-photo face path
 from .resample import ResampleItem  # vsp_resample_item: defined beside the plan that fills it, importable without the library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -195,6 +195,9 @@ SIGNATURES = {
     "vsp_niqe_features_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "vsp_face_crop_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
     "vsp_face_paste_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p, C.c_size_t, _p, _p, _i, _p],
+    "vsp_face_crop_aa_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
+    "vsp_face_paste_aa_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p,
+                             C.c_size_t, _p, _p, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
@@ -226,7 +229,7 @@ def _load():
     if lib.vsp_abi_version() != ABI_VERSION:
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
-                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile)):
+                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -38,6 +38,7 @@ int vsp_struct_size(int which) {
     case 7: return (int)sizeof(vsp_resample_item);
     case 8: return (int)sizeof(vsp_face_item);
     case 9: return (int)sizeof(vsp_face_tile);
+    case 10: return (int)sizeof(vsp_face_aa_item);
     default: return -1;
   }
 }

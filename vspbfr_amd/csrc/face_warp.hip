@@ -16,8 +16,14 @@
 // The source footprint of a tile is not staged in LDS: it is a variable-size parallelogram, and the 12 byte loads of a pixel hit lines
 // its neighbours in the tile have just pulled into the CU's L1 (tools/bench_photo.py times both kernels).
 //
+// The two *_aa entries are supersets: a face whose item carries reach > 0 is resampled by a tent filter one DESTINATION pixel
+// wide, evaluated at the source lattice points of a (2 reach + 2)^2 window around the bilinear centre cell (forward tables source ->
+// destination, also built by the host); a face with reach == 0 takes the four-tap path above, bit for bit.  tests/photo_aa_ref.py.
+//
 // Bounds: the entries check every item, table entry, tile and ramp value on the host against the buffer sizes they are given before
 // anything is launched; the kernels index tables only inside [0, nx) / [0, ny) of an item and pixels only inside a tile's photo.
+#include <algorithm>
+
 #include "vsp_common.h"
 
 namespace {
@@ -189,6 +195,202 @@ __global__ __launch_bounds__(kThreads) void face_paste_kernel(uint8_t* photos, c
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- anti-aliased
+// The tent filter of one destination pixel (dx, dy: absolute destination coordinates) over the window of source lattice points
+// ix - R .. ix + R + 1, iy - R .. iy + R + 1 around its bilinear centre cell:
+//     U = fu[qx] + gu[qy], V = fv[qx] + gv[qy], tu = max(0, 1024 - |U - 1024 dx|), tv likewise, w = (tu tv) >> 8,
+//     v_c = (sum w p_c + (W >> 1)) / W, W = sum w.
+// The differences are taken modulo 2^32: with |fu|, |gu| < 2^30 and 0 <= 1024 dx < 2^30 a true difference outside int32 wraps to a
+// magnitude above 2^30, which is a zero weight like the true one.  fu / fv are monotone in qx (rne of a linear function), so their
+// values at the two ends of the window bound a row's U and V: a row that cannot reach the pixel is culled with four compares.
+// CLAMP: pixel indices are clamped to the image (table indices never are); otherwise a point outside reads `border`.
+// The host entry has checked that the window of every served pixel lies inside the item's source range, so every table index is valid.
+template <bool CLAMP>
+__device__ __forceinline__ void filtered_rgb(const uint8_t* img, int w, int h, int X, int Y, int dx, int dy, const vsp_face_aa_item& it,
+                                             const int32_t* fwd, const int border[3], int v[3]) {
+  const int R = it.reach, nwin = 2 * R + 2;
+  const int qx0 = (X >> 5) - R, qy0 = (Y >> 5) - R;
+  const int32_t* fu = fwd + it.fwd_off + (qx0 - it.sx0);
+  const int32_t* fv = fu + it.snx;
+  const int32_t* gu = fwd + it.fwd_off + 2 * (int64_t)it.snx + (qy0 - it.sy0);
+  const int32_t* gv = gu + it.sny;
+  const unsigned tx = (unsigned)dx << 10, ty = (unsigned)dy << 10;
+  const int ulo = min(fu[0], fu[nwin - 1]), uhi = max(fu[0], fu[nwin - 1]);
+  const int vlo = min(fv[0], fv[nwin - 1]), vhi = max(fv[0], fv[nwin - 1]);
+  int acc0 = 0, acc1 = 0, acc2 = 0, W = 0;
+  for (int j = 0; j < nwin; ++j) {
+    const unsigned gus = (unsigned)gu[j] - tx, gvs = (unsigned)gv[j] - ty;
+    // the row's U - 1024 dx lies in [ulo + gus, uhi + gus]: no tap of it weighs anything unless that interval meets (-1024, 1024)
+    if ((int)((unsigned)uhi + gus) <= -1024 || (int)((unsigned)ulo + gus) >= 1024) continue;
+    if ((int)((unsigned)vhi + gvs) <= -1024 || (int)((unsigned)vlo + gvs) >= 1024) continue;
+    int yy = qy0 + j;
+    const bool row_in = (unsigned)yy < (unsigned)h;
+    if (CLAMP) yy = min(max(yy, 0), h - 1);
+    const uint8_t* rowp = img + (int64_t)yy * w * 3;
+    for (int i = 0; i < nwin; ++i) {
+      const unsigned du = (unsigned)fu[i] + gus, dv = (unsigned)fv[i] + gvs;
+      const unsigned au = (int)du < 0 ? 0u - du : du, av = (int)dv < 0 ? 0u - dv : dv;
+      if (au >= 1024u || av >= 1024u) continue;
+      const int wgt = (int)(((1024u - au) * (1024u - av)) >> 8);
+      if (wgt == 0) continue;
+      int xx = qx0 + i;
+      bool in = true;
+      if (CLAMP)
+        xx = min(max(xx, 0), w - 1);
+      else
+        in = row_in && (unsigned)xx < (unsigned)w;
+      if (in) {
+        const uint8_t* p = rowp + xx * 3;
+        acc0 += wgt * (int)p[0];
+        acc1 += wgt * (int)p[1];
+        acc2 += wgt * (int)p[2];
+      } else {
+        acc0 += wgt * border[0];
+        acc1 += wgt * border[1];
+        acc2 += wgt * border[2];
+      }
+      W += wgt;
+    }
+  }
+  // W > 0 for the tables of a similarity; the guard keeps a division by zero out of reach of any other table
+  const unsigned Wd = (unsigned)max(W, 1), half = (unsigned)W >> 1;
+  v[0] = (int)(((unsigned)acc0 + half) / Wd);
+  v[1] = (int)(((unsigned)acc1 + half) / Wd);
+  v[2] = (int)(((unsigned)acc2 + half) / Wd);
+}
+
+// face_crop_kernel with the per-face choice of the resampler: same grid, same thread shape, same stores.
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void face_crop_aa_kernel(uint8_t* out_u8, float* out_f32, const uint8_t* src, const int32_t* tables,
+                                                                 const int32_t* fwd, const vsp_face_aa_item* items, int S, int b0, int b1, int b2) {
+  const vsp_face_aa_item it = items[blockIdx.z];
+  const int y = (int)blockIdx.y * kTile + ((int)threadIdx.x >> 3);
+  const int xg = (int)blockIdx.x * kTile + ((int)threadIdx.x & 7) * 4;
+  if (y >= S || xg >= S) return;
+  const int32_t* ax = tables + it.tab_off;
+  const int32_t* bx = ax + S;
+  const int cxv = ax[2 * S + y], cyv = ax[3 * S + y];
+  const uint8_t* img = src + it.src_off;
+  const int border[3] = {b0, b1, b2};
+  int v[4][3];
+  if (it.reach == 0) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int x = min(xg + e, S - 1);
+      bilinear_rgb<false>(img, it.w, it.h, (cxv + ax[x]) >> 5, (cyv + bx[x]) >> 5, border, v[e]);
+    }
+  } else {
+    for (int e = 0; e < 4; ++e) {
+      const int x = min(xg + e, S - 1);
+      filtered_rgb<false>(img, it.w, it.h, (cxv + ax[x]) >> 5, (cyv + bx[x]) >> 5, x, y, it, fwd, border, v[e]);
+    }
+  }
+  const int64_t f = blockIdx.z;
+  if (out_u8) {
+    uint8_t* o = out_u8 + ((f * S + y) * S + xg) * 3;
+    if (VEC) {
+      uint32_t* o4 = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        uint32_t word = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+          const int j = 4 * k + b;
+          word |= (uint32_t)v[j / 3][j % 3] << (8 * b);
+        }
+        o4[k] = word;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (xg + e < S) {
+          o[3 * e + 0] = (uint8_t)v[e][0];
+          o[3 * e + 1] = (uint8_t)v[e][1];
+          o[3 * e + 2] = (uint8_t)v[e][2];
+        }
+      }
+    }
+  }
+  if (out_f32) {
+    const int64_t plane = (int64_t)S * S;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float* o = out_f32 + (f * 3 + c) * plane + (int64_t)y * S + xg;
+      float n[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) n[e] = __fdiv_rn(__fsub_rn(__fdiv_rn((float)v[e][c], 255.0f), 0.5f), 0.5f);
+      if (VEC) {
+        *reinterpret_cast<float4*>(o) = make_float4(n[0], n[1], n[2], n[3]);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (xg + e < S) o[e] = n[e];
+      }
+    }
+  }
+}
+
+// face_paste_kernel with the per-face choice of the resampler: same tile list, same walk in list order, same blend.
+__global__ __launch_bounds__(kThreads) void face_paste_aa_kernel(uint8_t* photos, const uint8_t* crops, const int32_t* tables, const int32_t* fwd,
+                                                                  const vsp_face_aa_item* items, const vsp_face_tile* tiles,
+                                                                  const int32_t* tile_faces, const uint16_t* ramp, int L, int S) {
+  const vsp_face_tile t = tiles[blockIdx.x];
+  const int y = t.y0 + ((int)threadIdx.x >> 3);
+  const int xg = t.x0 + ((int)threadIdx.x & 7) * 4;
+  if (y >= t.h || xg >= t.w) return;
+  uint8_t* row = photos + t.dst_off + ((int64_t)y * t.w + xg) * 3;
+  const int npx = min(4, t.w - xg);
+  int px[4][3];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < npx) {
+      px[e][0] = row[3 * e + 0];
+      px[e][1] = row[3 * e + 1];
+      px[e][2] = row[3 * e + 2];
+    } else {
+      px[e][0] = px[e][1] = px[e][2] = 0;
+    }
+  }
+  const int lim = (S - 1) * 32;
+  const int none[3] = {0, 0, 0};
+  bool touched = false;
+  for (int k = 0; k < t.nfaces; ++k) {
+    const vsp_face_aa_item it = items[tile_faces[t.face0 + k]];
+    const int ry = y - it.y0;
+    if (ry < 0 || ry >= it.ny) continue;
+    const int32_t* ax = tables + it.tab_off;
+    const int32_t* bx = ax + it.nx;
+    const int cxv = ax[2 * it.nx + ry], cyv = ax[2 * it.nx + it.ny + ry];
+    const uint8_t* crop = crops + it.src_off;
+    for (int e = 0; e < 4; ++e) {
+      const int rx = xg + e - it.x0;
+      if (e >= npx || rx < 0 || rx >= it.nx) continue;
+      const int X = (cxv + ax[rx]) >> 5, Y = (cyv + bx[rx]) >> 5;
+      const int d = min(min(X, Y), min(lim - X, lim - Y));
+      if (d < 0) continue;
+      const int w = ramp[min(d >> 2, L - 1)];
+      if (w == 0) continue;   // (256 bg + 128) >> 8 = bg
+      int f[3];
+      if (it.reach == 0)
+        bilinear_rgb<true>(crop, S, S, X, Y, none, f);
+      else
+        filtered_rgb<true>(crop, S, S, X, Y, xg + e, y, it, fwd, none, f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) px[e][c] = (w * f[c] + (256 - w) * px[e][c] + 128) >> 8;
+      touched = true;
+    }
+  }
+  if (!touched) return;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (e < npx) {
+      row[3 * e + 0] = (uint8_t)px[e][0];
+      row[3 * e + 1] = (uint8_t)px[e][1];
+      row[3 * e + 2] = (uint8_t)px[e][2];
+    }
+  }
+}
+
 // every entry of one face's tables below 2^30 in magnitude (so that cx + ax cannot wrap) and inside the table buffer
 int check_tables(const char* what, int i, const vsp_face_item& it, const int32_t* tables, size_t table_ints) {
   VSP_REQUIRE(it.nx >= 0 && it.ny >= 0 && it.nx <= VSP_FACE_MAX_SIDE && it.ny <= VSP_FACE_MAX_SIDE, "%s: face %d: table extents %d x %d", what,
@@ -204,6 +406,54 @@ int check_tables(const char* what, int i, const vsp_face_item& it, const int32_t
 }
 
 constexpr uint64_t kTwoGiB = 1ull << 31;
+
+// One anti-aliased item: its destination -> source tables as check_tables does, then reach (VSP_ENOTSUP above VSP_FACE_AA_MAX_REACH), the
+// forward tables (inside the buffer, every entry below 2^30) and the source range: the centre cell of any pixel the item serves is
+// ((cx[y] + ax[x]) >> 10, (cy[y] + bx[x]) >> 10), which lies between the cells of (min cx + min ax) and (max cx + max ax) -- the range
+// must hold those extremes - reach .. + reach + 1.
+int check_aa_item(const char* what, int i, const vsp_face_aa_item& a, const int32_t* tables, size_t table_ints, const int32_t* fwd,
+                  size_t fwd_ints) {
+  vsp_face_item it;
+  it.src_off = a.src_off, it.tab_off = a.tab_off, it.h = a.h, it.w = a.w, it.x0 = a.x0, it.y0 = a.y0, it.nx = a.nx, it.ny = a.ny;
+  const int rc = check_tables(what, i, it, tables, table_ints);
+  if (rc != VSP_OK) return rc;
+  VSP_REQUIRE(a.reach >= 0, "%s: face %d: reach %d", what, i, a.reach);
+  if (a.reach > VSP_FACE_AA_MAX_REACH)
+    return vsp::fail(VSP_ENOTSUP, "%s: face %d: reach %d above %d (a minification above 16 is not served)", what, i, a.reach, VSP_FACE_AA_MAX_REACH);
+  if (a.reach == 0 || a.nx == 0 || a.ny == 0) return VSP_OK;
+  VSP_REQUIRE(fwd, "%s: null pointer (forward tables of face %d)", what, i);
+  VSP_REQUIRE(a.snx > 0 && a.sny > 0 && a.snx <= VSP_FACE_AA_MAX_RANGE && a.sny <= VSP_FACE_AA_MAX_RANGE, "%s: face %d: source range of %d x %d", what,
+              i, a.snx, a.sny);
+  VSP_REQUIRE(a.sx0 > -kTableLimit && a.sx0 < kTableLimit && a.sy0 > -kTableLimit && a.sy0 < kTableLimit, "%s: face %d: source range at (%d, %d)",
+              what, i, a.sx0, a.sy0);
+  VSP_REQUIRE(a.x0 >= 0 && a.y0 >= 0 && (int64_t)a.x0 + a.nx <= (1 << 20) && (int64_t)a.y0 + a.ny <= (1 << 20),
+              "%s: face %d: a filtered face's destination must stay below 2^20 pixels a side", what, i);
+  const uint64_t n = 2ull * (uint64_t)a.snx + 2ull * (uint64_t)a.sny;
+  VSP_REQUIRE(a.fwd_off >= 0 && (uint64_t)a.fwd_off + n <= (uint64_t)fwd_ints, "%s: face %d: forward tables outside the %zu entries", what, i,
+              fwd_ints);
+  const int32_t* f = fwd + a.fwd_off;
+  for (uint64_t k = 0; k < n; ++k)
+    VSP_REQUIRE(f[k] > -kTableLimit && f[k] < kTableLimit, "%s: face %d: table overflow (forward entry %llu = %d, magnitude 2^30 or more)", what, i,
+                (unsigned long long)k, f[k]);
+  const int32_t* t = tables + a.tab_off;
+  int64_t lo[4], hi[4];   // ax, bx, cx, cy
+  const int len[4] = {a.nx, a.nx, a.ny, a.ny};
+  for (int q = 0; q < 4; ++q) {
+    lo[q] = hi[q] = t[0];
+    for (int k = 0; k < len[q]; ++k) {
+      lo[q] = std::min<int64_t>(lo[q], t[k]);
+      hi[q] = std::max<int64_t>(hi[q], t[k]);
+    }
+    t += len[q];
+  }
+  const int64_t ix0 = (lo[2] + lo[0]) >> 10, ix1 = (hi[2] + hi[0]) >> 10, iy0 = (lo[3] + lo[1]) >> 10, iy1 = (hi[3] + hi[1]) >> 10;
+  VSP_REQUIRE(ix0 - a.reach >= a.sx0 && ix1 + a.reach + 1 < (int64_t)a.sx0 + a.snx && iy0 - a.reach >= a.sy0 &&
+                  iy1 + a.reach + 1 < (int64_t)a.sy0 + a.sny,
+              "%s: face %d: source range too small (columns %d + %d, rows %d + %d; windows reach columns %lld .. %lld, rows %lld .. %lld)", what, i,
+              a.sx0, a.snx, a.sy0, a.sny, (long long)(ix0 - a.reach), (long long)(ix1 + a.reach + 1), (long long)(iy0 - a.reach),
+              (long long)(iy1 + a.reach + 1));
+  return VSP_OK;
+}
 
 }  // namespace
 
@@ -298,6 +548,102 @@ int vsp_face_paste_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops,
   face_paste_kernel<<<dim3((unsigned)ntiles), kThreads, 0, vsp::as_stream(stream)>>>(photos, crops, tables_dev, items_dev, tiles_dev,
                                                                                      tile_faces_dev, ramp_dev, ramp_len, S);
   return vsp::check_launch("face_paste");
+}
+
+int vsp_face_crop_aa_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, size_t src_bytes, const int32_t* tables, const int32_t* tables_dev,
+                        size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints, const vsp_face_aa_item* items,
+                        const vsp_face_aa_item* items_dev, int n, int S, int border_r, int border_g, int border_b, vsp_stream_t stream) {
+  VSP_REQUIRE(n >= 0 && n <= VSP_FACE_MAX_ITEMS, "face_crop_aa: 0..%d faces (got %d)", VSP_FACE_MAX_ITEMS, n);
+  VSP_REQUIRE(S > 0 && S <= VSP_FACE_MAX_SIDE, "face_crop_aa: crop side 1..%d (got %d)", VSP_FACE_MAX_SIDE, S);
+  VSP_REQUIRE((unsigned)border_r < 256u && (unsigned)border_g < 256u && (unsigned)border_b < 256u, "face_crop_aa: border colour outside 0..255");
+  if (n == 0) return VSP_OK;
+  VSP_REQUIRE(out_u8 || out_f32, "face_crop_aa: null pointer (no output)");
+  VSP_REQUIRE(src && tables && tables_dev && items && items_dev && (fwd == nullptr) == (fwd_dev == nullptr), "face_crop_aa: null pointer");
+  VSP_REQUIRE((reinterpret_cast<uintptr_t>(tables_dev) & 3u) == 0 && (reinterpret_cast<uintptr_t>(fwd_dev) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(items_dev) & 7u) == 0 && (reinterpret_cast<uintptr_t>(out_f32) & 3u) == 0,
+              "face_crop_aa: misaligned tables, items or fp32 output");
+  VSP_REQUIRE((uint64_t)src_bytes < kTwoGiB && (uint64_t)n * S * S * 3ull < kTwoGiB && (uint64_t)fwd_ints * 4ull < kTwoGiB,
+              "face_crop_aa: the photos and the tables must stay below 2 GiB and an output below 2^31 elements (%d faces of %d x %d)", n, S, S);
+  for (int i = 0; i < n; ++i) {
+    const vsp_face_aa_item& it = items[i];
+    VSP_REQUIRE(it.w > 0 && it.h > 0, "face_crop_aa: face %d: photo size %d x %d", i, it.w, it.h);
+    VSP_REQUIRE(it.src_off >= 0 && (uint64_t)it.src_off + 3ull * (uint64_t)it.w * (uint64_t)it.h <= (uint64_t)src_bytes,
+                "face_crop_aa: face %d: photo outside the %zu source bytes", i, src_bytes);
+    VSP_REQUIRE(it.nx == S && it.ny == S && it.x0 == 0 && it.y0 == 0, "face_crop_aa: face %d: tables of %d x %d at (%d, %d) for a crop of side %d", i,
+                it.nx, it.ny, it.x0, it.y0, S);
+    const int rc = check_aa_item("face_crop_aa", i, it, tables, table_ints, fwd, fwd_ints);
+    if (rc != VSP_OK) return rc;
+  }
+  const unsigned tiles = (unsigned)((S + kTile - 1) / kTile);
+  const dim3 grid(tiles, tiles, (unsigned)n);
+  const bool vec = S % 4 == 0 && (reinterpret_cast<uintptr_t>(out_u8) & 3u) == 0 && (reinterpret_cast<uintptr_t>(out_f32) & 15u) == 0;
+  hipStream_t s = vsp::as_stream(stream);
+  if (vec)
+    face_crop_aa_kernel<true><<<grid, kThreads, 0, s>>>(out_u8, out_f32, src, tables_dev, fwd_dev, items_dev, S, border_r, border_g, border_b);
+  else
+    face_crop_aa_kernel<false><<<grid, kThreads, 0, s>>>(out_u8, out_f32, src, tables_dev, fwd_dev, items_dev, S, border_r, border_g, border_b);
+  return vsp::check_launch("face_crop_aa");
+}
+
+int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                         const int32_t* tables_dev, size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints,
+                         const vsp_face_aa_item* items, const vsp_face_aa_item* items_dev, int n, int S, const vsp_face_tile* tiles,
+                         const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
+                         size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, vsp_stream_t stream) {
+  VSP_REQUIRE(n >= 0 && n <= VSP_FACE_MAX_ITEMS, "face_paste_aa: 0..%d faces (got %d)", VSP_FACE_MAX_ITEMS, n);
+  VSP_REQUIRE(S > 0 && S <= VSP_FACE_MAX_SIDE, "face_paste_aa: crop side 1..%d (got %d)", VSP_FACE_MAX_SIDE, S);
+  VSP_REQUIRE(ntiles >= 0, "face_paste_aa: %d tiles", ntiles);
+  VSP_REQUIRE(ramp && ramp_dev, "face_paste_aa: null pointer (ramp)");
+  VSP_REQUIRE(ramp_len >= 1 && ramp_len <= VSP_FACE_MAX_RAMP, "face_paste_aa: ramp of 1..%d entries (got %d)", VSP_FACE_MAX_RAMP, ramp_len);
+  VSP_REQUIRE(ramp[0] == 0, "face_paste_aa: ramp[0] != 0 (the crop border itself must keep the background; got %d)", (int)ramp[0]);
+  for (int k = 0; k < ramp_len; ++k) VSP_REQUIRE(ramp[k] <= 256, "face_paste_aa: ramp[%d] = %d above 256", k, (int)ramp[k]);
+  if (n == 0 || ntiles == 0) return VSP_OK;
+  VSP_REQUIRE(photos && crops && tables && tables_dev && items && items_dev && tiles && tiles_dev && tile_faces && tile_faces_dev &&
+                  (fwd == nullptr) == (fwd_dev == nullptr),
+              "face_paste_aa: null pointer");
+  VSP_REQUIRE((reinterpret_cast<uintptr_t>(tables_dev) & 3u) == 0 && (reinterpret_cast<uintptr_t>(fwd_dev) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(items_dev) & 7u) == 0 && (reinterpret_cast<uintptr_t>(tiles_dev) & 7u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(tile_faces_dev) & 3u) == 0 && (reinterpret_cast<uintptr_t>(ramp_dev) & 1u) == 0,
+              "face_paste_aa: misaligned tables, items, tiles or ramp");
+  VSP_REQUIRE((uint64_t)photo_bytes < kTwoGiB && (uint64_t)crop_bytes < kTwoGiB && (uint64_t)fwd_ints * 4ull < kTwoGiB,
+              "face_paste_aa: the photos, the crops and the tables must each stay below 2 GiB");
+  const uint64_t one = 3ull * (uint64_t)S * (uint64_t)S;
+  for (int i = 0; i < n; ++i) {
+    const vsp_face_aa_item& it = items[i];
+    VSP_REQUIRE(it.w == S && it.h == S, "face_paste_aa: face %d: its source is the %d x %d crop (got %d x %d)", i, S, S, it.w, it.h);
+    VSP_REQUIRE(it.src_off >= 0 && (uint64_t)it.src_off + one <= (uint64_t)crop_bytes, "face_paste_aa: face %d: crop outside the %zu crop bytes", i,
+                crop_bytes);
+    VSP_REQUIRE(it.x0 >= 0 && it.y0 >= 0, "face_paste_aa: face %d: bounding box at (%d, %d)", i, it.x0, it.y0);
+    const int rc = check_aa_item("face_paste_aa", i, it, tables, table_ints, fwd, fwd_ints);
+    if (rc != VSP_OK) return rc;
+  }
+  for (int k = 0; k < ntiles; ++k) {
+    const vsp_face_tile& t = tiles[k];
+    VSP_REQUIRE(t.w > 0 && t.h > 0 && t.dst_off >= 0 && (uint64_t)t.dst_off + 3ull * (uint64_t)t.w * (uint64_t)t.h <= (uint64_t)photo_bytes,
+                "face_paste_aa: tile %d: photo outside the %zu photo bytes", k, photo_bytes);
+    VSP_REQUIRE(t.x0 >= 0 && t.y0 >= 0 && t.x0 % kTile == 0 && t.y0 % kTile == 0 && t.x0 < t.w && t.y0 < t.h,
+                "face_paste_aa: tile %d at (%d, %d) of a %d x %d photo", k, t.x0, t.y0, t.w, t.h);
+    if (k > 0) {   // strictly ascending (photo, row, column): a tile appears once, so one thread owns a pixel
+      const vsp_face_tile& p = tiles[k - 1];
+      const bool same = p.dst_off == t.dst_off;
+      VSP_REQUIRE(same ? (p.w == t.w && p.h == t.h && (p.y0 < t.y0 || (p.y0 == t.y0 && p.x0 < t.x0)))
+                       : (uint64_t)p.dst_off + 3ull * (uint64_t)p.w * (uint64_t)p.h <= (uint64_t)t.dst_off,
+                  "face_paste_aa: tile %d: tiles must ascend by photo, row, column without repeats or overlapping photos", k);
+    }
+    VSP_REQUIRE(t.nfaces >= 1 && t.face0 >= 0 && (uint64_t)t.face0 + (uint64_t)t.nfaces <= (uint64_t)tile_face_ints,
+                "face_paste_aa: tile %d: face list outside the %zu entries", k, tile_face_ints);
+    for (int j = 0; j < t.nfaces; ++j) {
+      const int f = tile_faces[t.face0 + j];
+      VSP_REQUIRE(f >= 0 && f < n && (j == 0 || tile_faces[t.face0 + j - 1] < f), "face_paste_aa: tile %d: faces must be 0..%d in list order", k,
+                  n - 1);
+      const vsp_face_aa_item& it = items[f];
+      VSP_REQUIRE((int64_t)it.x0 + it.nx <= t.w && (int64_t)it.y0 + it.ny <= t.h, "face_paste_aa: tile %d: face %d's bounding box leaves the photo", k,
+                  f);
+    }
+  }
+  face_paste_aa_kernel<<<dim3((unsigned)ntiles), kThreads, 0, vsp::as_stream(stream)>>>(photos, crops, tables_dev, fwd_dev, items_dev, tiles_dev,
+                                                                                        tile_faces_dev, ramp_dev, ramp_len, S);
+  return vsp::check_launch("face_paste_aa");
 }
 
 }  // extern "C"

@@ -4,7 +4,8 @@
                                 FFHQ 512^2 template; float64, NumPy
     FacePlan                    one ragged batch of photos and their faces: the int32 coordinate tables of both kernels, the item and
                                 tile tables, the packed photo bytes -- the counterpart of resample.ResamplePlan
-    crop_faces / paste_faces    vsp_face_crop_u8 / vsp_face_paste_u8 on a plan
+    crop_faces / paste_faces    vsp_face_crop_u8 / vsp_face_paste_u8 on a plan (the *_aa entries for a plan built with antialias=True:
+                                a face that is minified is resampled by a tent filter one destination pixel wide)
     PhotoRestorer               photos + landmarks -> photos with their faces restored by a RestorationPipeline
 
 All device arithmetic is integer: the float64 geometry ends in the tables built here (`face_tables`), which tests/photo_ref.py restates.
@@ -30,11 +31,19 @@ MAX_RAMP = 65536               # VSP_FACE_MAX_RAMP
 TABLE_LIMIT = 1 << 30          # a table entry of this magnitude is refused (cx + ax must not wrap)
 DEFAULT_BORDER = (128, 128, 128)
 DEFAULT_INSET, DEFAULT_FEATHER = 8, 48     # px; design choices, not measurements
+MAX_MINIFY = 16                # the largest minification the filtered kernels serve (int32 accumulator)
+MAX_REACH = 23                 # VSP_FACE_AA_MAX_REACH = ceil(16 sqrt(2) + 0.125)
 
 
 class FaceItem(C.Structure):
     """include/vspbfr_hip.h vsp_face_item"""
     _fields_ = [("src_off", C.c_int64), ("tab_off", C.c_int64)] + [(n, C.c_int32) for n in ("h", "w", "x0", "y0", "nx", "ny")]
+
+
+class FaceAAItem(C.Structure):
+    """include/vspbfr_hip.h vsp_face_aa_item"""
+    _fields_ = ([("src_off", C.c_int64), ("tab_off", C.c_int64), ("fwd_off", C.c_int64)]
+                + [(n, C.c_int32) for n in ("h", "w", "x0", "y0", "nx", "ny", "sx0", "sy0", "snx", "sny", "reach", "pad_")])
 
 
 class FaceTile(C.Structure):
@@ -101,6 +110,58 @@ def face_tables(M, xs, ys, photo="?", face=0):
     return t.astype(np.int32)
 
 
+def crop_minify(A):
+    """source pixels per crop pixel: 1 / |A|, |A| the similarity's scale"""
+    return 1.0 / float(np.hypot(A[0, 0], A[1, 0]))
+
+
+def paste_minify(P):
+    """crop pixels per output pixel: |P| = |A| / upscale"""
+    return float(np.hypot(P[0, 0], P[1, 0]))
+
+
+def filter_reach(M, m):
+    """0 for a face that is not minified (m <= 1: four-tap bilinear), else ceil(|M00| + |M01| + 0.125) for M (destination -> source):
+    every source lattice point with a non-zero tent weight lies in columns ix - reach .. ix + reach + 1 of the centre cell, rows
+    likewise (|M10| + |M11| is the same number for a similarity)"""
+    return 0 if m <= 1.0 else int(np.ceil(abs(float(M[0, 0])) + abs(float(M[0, 1])) + 0.125))
+
+
+def forward_tables(F, qxs, qys, photo="?", face=0):
+    """The int32 forward tables of one filtered face for F (2 x 3 float64, source -> destination), source columns qxs and rows qys,
+    concatenated as the kernels read them: fu[snx], fv[snx], gu[sny], gv[sny] (include/vspbfr_hip.h).  No rounding offset: U = fu + gu
+    is the destination coordinate of a source lattice point in Q10."""
+    F = np.asarray(F, dtype=np.float64)
+    qxs, qys = np.asarray(qxs, dtype=np.float64), np.asarray(qys, dtype=np.float64)
+    t = np.concatenate((np.rint(F[0, 0] * qxs * 1024.0), np.rint(F[1, 0] * qxs * 1024.0), np.rint((F[0, 1] * qys + F[0, 2]) * 1024.0),
+                        np.rint((F[1, 1] * qys + F[1, 2]) * 1024.0)))
+    if t.size and not np.all(np.abs(t) < TABLE_LIMIT):
+        raise ValueError(f"{_where(photo, face)}: the face lies too far outside the photo (a forward table entry reaches 2^30)")
+    return t.astype(np.int32)
+
+
+def source_range(t, nx, ny, reach):
+    """(sx0, sy0, snx, sny): the source columns and rows that hold the filter window of every destination pixel of one face, from the
+    extremes of its destination -> source tables t = ax[nx], bx[nx], cx[ny], cy[ny] -- what the C entry checks"""
+    t = t.astype(np.int64)
+    ax, bx, cx, cy = t[:nx], t[nx:2 * nx], t[2 * nx:2 * nx + ny], t[2 * nx + ny:]
+    sx0, sx1 = ((int(cx.min()) + int(ax.min())) >> 10) - reach, ((int(cx.max()) + int(ax.max())) >> 10) + reach + 1
+    sy0, sy1 = ((int(cy.min()) + int(bx.min())) >> 10) - reach, ((int(cy.max()) + int(bx.max())) >> 10) + reach + 1
+    return sx0, sy0, sx1 - sx0 + 1, sy1 - sy0 + 1
+
+
+def check_minify(A, upscale=1, photo="?", face=0):
+    """(crop minification, paste minification) of one face; ValueError naming the photo and the face above MAX_MINIFY"""
+    mc, mp = crop_minify(A), paste_minify(paste_matrix(A, upscale))
+    if mc > MAX_MINIFY:
+        raise ValueError(f"{_where(photo, face)}: the face is {mc:.1f} times larger than the crop; the anti-aliased crop serves at most "
+                         f"{MAX_MINIFY} (shrink the photo first)")
+    if mp > MAX_MINIFY:
+        raise ValueError(f"{_where(photo, face)}: the crop is {mp:.1f} times larger than the face in the output photo; the anti-aliased "
+                         f"paste serves at most {MAX_MINIFY}")
+    return mc, mp
+
+
 def face_bbox(P, S, H, W):
     """(x0, y0, x1, y1), ends exclusive: the corners of the crop square [0, S - 1]^2 taken back through P into the (H, W) output photo,
     floor / ceil with one pixel of margin (the tables are rounded), clipped to the photo.  Empty (x1 <= x0 or y1 <= y0) where the face
@@ -133,10 +194,14 @@ class FacePlan:
     For face i: A_i = similarity_from_landmarks; the crop tables of M = A^-1 over the S x S crop; P = paste_matrix(A, upscale), its
     bounding box in the (upscale h, upscale w) output photo and the paste tables over that box.  The paste tiles: every 32 x 32 tile of
     the output photos' tile grids that a box meets, ascending by (photo, row, column), each with its faces in list order.
-    `names` (one per photo) appear in error messages."""
+    `names` (one per photo) appear in error messages.
 
-    def __init__(self, photos, faces, size=512, upscale=1, names=None):
-        self.S, self.upscale = int(size), int(upscale)
+    antialias=True adds, per face and kernel, the minification m (crop: 1 / |A|, paste: |A| / upscale), reach (0 where m <= 1: that face
+    keeps the four bilinear taps), the forward tables over the source range its filter windows touch and a vsp_face_aa_item; a
+    minification above MAX_MINIFY is a ValueError.  Without it nothing of this is computed and pack() is unchanged."""
+
+    def __init__(self, photos, faces, size=512, upscale=1, names=None, antialias=False):
+        self.S, self.upscale, self.antialias = int(size), int(upscale), bool(antialias)
         if not 1 <= self.S <= MAX_SIDE or self.upscale < 1:
             raise ValueError(f"FacePlan: size {size}, upscale {upscale}")
         if len(faces) > MAX_ITEMS:
@@ -162,6 +227,23 @@ class FacePlan:
         self.face_photo, self.A, self.P, self.boxes = [], [], [], []
         self.crop_items, self.paste_items = (FaceItem * max(n, 1))(), (FaceItem * max(n, 1))()
         crop_tabs, paste_tabs, ct, pt = [], [], 0, 0
+        if self.antialias:
+            self.crop_aa_items, self.paste_aa_items = (FaceAAItem * max(n, 1))(), (FaceAAItem * max(n, 1))()
+            self.crop_minify, self.paste_minify = [], []
+            fwd = {"crop": [], "paste": []}
+            fwd_n = {"crop": 0, "paste": 0}
+
+        def aa_item(kind, dst, it, t, M, F, m, where):
+            """the vsp_face_aa_item of one face for one kernel: `it` plus reach, source range and forward tables"""
+            for name in ("src_off", "tab_off", "h", "w", "x0", "y0", "nx", "ny"):
+                setattr(dst, name, getattr(it, name))
+            reach = filter_reach(M, m) if it.nx > 0 and it.ny > 0 else 0
+            dst.reach, dst.fwd_off = reach, fwd_n[kind]
+            if reach:
+                dst.sx0, dst.sy0, dst.snx, dst.sny = source_range(t, it.nx, it.ny, reach)
+                f = forward_tables(F, np.arange(dst.sx0, dst.sx0 + dst.snx), np.arange(dst.sy0, dst.sy0 + dst.sny), *where)
+                fwd[kind].append(f)
+                fwd_n[kind] += f.size
         per_photo = {}
         which = {}
         for i, (k, pts) in enumerate(faces):
@@ -180,20 +262,32 @@ class FacePlan:
             self.A.append(A)
             self.P.append(P)
             self.boxes.append((x0, y0, x1, y1))
-            t = face_tables(invert_affine(A), np.arange(S), np.arange(S), names[k], j)
+            if self.antialias:
+                mc, mp = check_minify(A, self.upscale, names[k], j)
+                self.crop_minify.append(mc)
+                self.paste_minify.append(mp)
+            Ai = invert_affine(A)
+            t = face_tables(Ai, np.arange(S), np.arange(S), names[k], j)
             it = self.crop_items[i]
             it.src_off, it.tab_off, it.h, it.w, it.x0, it.y0, it.nx, it.ny = self.src_off[k], ct, h, w, 0, 0, S, S
             crop_tabs.append(t)
             ct += t.size
+            if self.antialias:
+                aa_item("crop", self.crop_aa_items[i], it, t, Ai, A, mc, (names[k], j))
             t = face_tables(P, np.arange(x0, x1), np.arange(y0, y1), names[k], j)
             it = self.paste_items[i]
             it.src_off, it.tab_off, it.h, it.w, it.x0, it.y0, it.nx, it.ny = i * 3 * S * S, pt, S, S, x0, y0, x1 - x0, y1 - y0
             paste_tabs.append(t)
             pt += t.size
+            if self.antialias:
+                aa_item("paste", self.paste_aa_items[i], it, t, P, invert_affine(P), mp, (names[k], j))
             if x1 > x0:
                 per_photo.setdefault(k, []).append(i)
         self.crop_tables = np.concatenate(crop_tabs) if crop_tabs else np.zeros(0, dtype=np.int32)
         self.paste_tables = np.concatenate(paste_tabs) if paste_tabs else np.zeros(0, dtype=np.int32)
+        if self.antialias:
+            self.crop_fwd = np.concatenate(fwd["crop"]) if fwd["crop"] else np.zeros(0, dtype=np.int32)
+            self.paste_fwd = np.concatenate(fwd["paste"]) if fwd["paste"] else np.zeros(0, dtype=np.int32)
         tiles, tile_faces = [], []
         for k in sorted(per_photo):
             oh, ow = self.out_shape[k]
@@ -226,6 +320,10 @@ class FacePlan:
                      ("tiles", np.frombuffer(bytes(self.tiles), dtype=np.uint8)[:nt * C.sizeof(FaceTile)]),
                      ("tile_faces", self.tile_faces.view(np.uint8)), ("crop_tables", self.crop_tables.view(np.uint8)),
                      ("paste_tables", self.paste_tables.view(np.uint8))]
+            if self.antialias:                              # extra sections; without them the buffer is what it always was
+                parts += [("crop_aa_items", np.frombuffer(bytes(self.crop_aa_items), dtype=np.uint8)[:n * C.sizeof(FaceAAItem)]),
+                          ("paste_aa_items", np.frombuffer(bytes(self.paste_aa_items), dtype=np.uint8)[:n * C.sizeof(FaceAAItem)]),
+                          ("crop_fwd", self.crop_fwd.view(np.uint8)), ("paste_fwd", self.paste_fwd.view(np.uint8))]
             sections, off = {}, 0
             for name, a in parts:
                 sections[name] = (off, a.size)
@@ -278,6 +376,8 @@ def crop_faces(plan, device, u8=True, f32=False, border=DEFAULT_BORDER):
     """The aligned crops of every face of the plan on `device`, current stream -> (u8 (F, S, S, 3) or None, f32 (F, 3, S, S) or None)."""
     from . import hip_ops
     dev = plan.upload(device)
+    if plan.antialias:
+        return hip_ops.face_crop_aa_u8(plan, dev["crop_aa_items"], dev["crop_tables"], dev["crop_fwd"], dev["photos"], border=border, u8=u8, f32=f32)
     return hip_ops.face_crop_u8(plan, dev["crop_items"], dev["crop_tables"], dev["photos"], border=border, u8=u8, f32=f32)
 
 
@@ -298,19 +398,26 @@ def paste_faces(plan, restored_u8, device, ramp=None, out=None):
     ramp_dev = plan._ramps.get(key)              # a plan pasted more than once uploads its ramp once
     if ramp_dev is None:
         ramp_dev = plan._ramps[key] = torch.from_numpy(ramp.view(np.int16).copy()).to(device)
-    hip_ops.face_paste_u8(plan, out, restored_u8, dev["paste_items"], dev["paste_tables"], dev["tiles"], dev["tile_faces"], ramp, ramp_dev)
+    if plan.antialias:
+        hip_ops.face_paste_aa_u8(plan, out, restored_u8, dev["paste_aa_items"], dev["paste_tables"], dev["paste_fwd"], dev["tiles"],
+                                 dev["tile_faces"], ramp, ramp_dev)
+    else:
+        hip_ops.face_paste_u8(plan, out, restored_u8, dev["paste_items"], dev["paste_tables"], dev["tiles"], dev["tile_faces"], ramp, ramp_dev)
     return out
 
 
 class PhotoRestorer:
     """photos + five-point landmarks -> the photos with every face restored.  The photos stay on the device: crop (vsp_face_crop_u8),
     `pipe` (a RestorationPipeline) over the faces of all photos in batches of `batch`, quantisation to uint8 as PngWriter does
-    (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4."""
+    (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4.
+    antialias=True: the anti-aliased entries for crop and paste."""
 
-    def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER):
+    def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER,
+                 antialias=False):
         if int(upscale) not in (1, 2, 4) or int(batch) < 1:
             raise ValueError(f"PhotoRestorer: batch {batch}, upscale {upscale}")
         self.pipe, self.batch, self.upscale, self.size, self.border = pipe, int(batch), int(upscale), int(size), tuple(border)
+        self.antialias = bool(antialias)       # minified faces through the tent filter of DESIGN 16, crop and paste
         self.ramp = default_ramp(inset, feather)
 
     def __call__(self, photos, landmarks, device, names=None):
@@ -320,7 +427,7 @@ class PhotoRestorer:
 
         from . import hip_ops
         faces = [(k, pts) for k, per in enumerate(landmarks) for pts in (per or [])]
-        plan = FacePlan(photos, faces, self.size, self.upscale, names)
+        plan = FacePlan(photos, faces, self.size, self.upscale, names, antialias=self.antialias)
         S = self.size
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)

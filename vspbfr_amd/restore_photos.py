@@ -1,7 +1,7 @@
 """Restore the faces inside whole photos and give the photos back.
 
     python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
-        [--inset PX] [--feather PX] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--inset PX] [--feather PX] [--antialias] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
@@ -17,6 +17,10 @@ faces are pasted at that scale.  Output: OUT/<relative stem>.png for every photo
 through (resized if asked) -- with --save_faces also <stem>_<k>_crop.png and <stem>_<k>_restore.png per face, and report.json
 (report_<rank>.json in a multi-GPU run) listing every photo with its face count.
 
+--antialias: a face larger than the crop is shrunk, and a restored crop larger than its face in the output photo is pasted, through a
+tent filter one destination pixel wide instead of four bilinear taps; report.json then lists per face `crop_minify` and
+`paste_minify`.  A minification above 16 is refused while the landmarks are validated.
+
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
 import argparse
@@ -28,16 +32,17 @@ import torch
 
 from .e4e import E4e_embedding
 from .imageio import PngWriter, list_images
-from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, similarity_from_landmarks
+from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, check_minify, similarity_from_landmarks
 from .pipeline import RestorationPipeline, load_ddpm, shard_range
 from .restorenet import Restoration_net
 
 MAX_PHOTOS_PER_CALL = 8      # photos decoded and kept on the device together while their faces fill a batch
 
 
-def load_landmarks(path, names):
+def load_landmarks(path, names, size=512, upscale=1, antialias=False):
     """FILE.json -> {relative name: [(5, 2) float64, ...]}; every face is validated here (ValueError names the photo and the face), an
-    entry for a photo that is not in the list is an error too"""
+    entry for a photo that is not in the list is an error too.  antialias: a minification above photo.MAX_MINIFY at crop side `size`
+    and `upscale` is refused here as well."""
     with open(path) as f:
         raw = json.load(f)
     if not isinstance(raw, dict):
@@ -50,7 +55,9 @@ def load_landmarks(path, names):
         if not isinstance(faces, list):
             raise ValueError(f"photo {name!r}: expected a list of faces")
         for k, pts in enumerate(faces):
-            similarity_from_landmarks(pts, photo=name, face=k)
+            A = similarity_from_landmarks(pts, size=size, photo=name, face=k)
+            if antialias:
+                check_minify(A, upscale, name, k)
         out[name] = [np.asarray(p, dtype=np.float64) for p in faces]
     return out
 
@@ -98,6 +105,9 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
                     writer.submit(restored[i:i + 1], [f"{stem}_{j}_restore.png"])
             report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ".png", args.out),
                            "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
+            if plan.antialias:
+                report[-1]["crop_minify"] = [round(plan.crop_minify[i], 6) for i in mine]
+                report[-1]["paste_minify"] = [round(plan.paste_minify[i], 6) for i in mine]
     writer.drain()
     name = "report.json" if world == 1 else "report_%d.json" % rank
     with open(os.path.join(args.out, name), "w") as f:
@@ -126,13 +136,15 @@ def main(argv=None):
     ap.add_argument("--save_faces", action="store_true", help="also write <stem>_<k>_crop.png and <stem>_<k>_restore.png")
     ap.add_argument("--inset", type=int, default=DEFAULT_INSET, help="px of the crop border that keep the photo")
     ap.add_argument("--feather", type=int, default=DEFAULT_FEATHER, help="px over which the blend rises to the restored face")
+    ap.add_argument("--antialias", action="store_true", help="shrink large faces into the crop, and restored crops into small faces, through a "
+                                                             "tent filter one destination pixel wide instead of four bilinear taps")
     args = ap.parse_args(argv)
     if args.batch < 1 or args.inset < 0 or args.feather < 0:
         ap.error("--batch must be at least 1, --inset and --feather at least 0")
     args.latent, args.n_mlp = 512, 8
     try:                       # the inputs are checked before any model is loaded
         names = list_photos(args.photos)
-        landmarks = load_landmarks(args.landmarks, names)
+        landmarks = load_landmarks(args.landmarks, names, args.size, args.upscale, args.antialias)
     except (ValueError, OSError) as e:
         ap.error(str(e))
     from . import hip_ops
@@ -154,7 +166,8 @@ def main(argv=None):
     psp = E4e_embedding(args.psp_checkpoint_path, out_size=args.size, size=1024, device=device, use_generator=True)
     diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
     pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)
-    restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather)
+    restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather,
+                             antialias=args.antialias)
     restore_photos(args, restorer, names, landmarks, device, rank, world)
 
 
