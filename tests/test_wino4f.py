@@ -52,7 +52,10 @@ def _ref(x, w, s_in=None, demod=None, bias1=None, bias2=None, nz=None, nw=0.0, r
     return y
 
 
-# F(4x4) with the points 0, +-3/4, +-3/2, inf: measured max 1.3e-5 ... 3.1e-5 relative to the output range at K = 64 ... 256 (the pair: the same)
+# A coarse bound against the output range, for geometry and epilogue mistakes.  What F(4x4) with the points 0, +-3/4, +-3/2, inf costs in
+# fp32 is measured and bounded in tests/test_wino_fence_gpu.py against a float32 model of the algorithm on the same operands
+# (profiles/wino_fence.json): max|d| = 0.3e-6 ... 3.2e-6 of max|ref|, 0.7 ... 1.5x the model's, on maps up to 128^2.  (An earlier
+# note here read 1.3e-5 ... 3.1e-5 "of the output range" at K = 64 ... 256: the size max|d| ITSELF has there, at max|ref| = 4 ... 7.)
 TOL = 6e-5
 
 
