@@ -932,6 +932,42 @@ int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* cro
                          const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
                          size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Colour fix for restored faces (csrc/color_fix.hip; bytes equal tests/color_fix_ref.py).  crop, restored, out: packed
+ * uint8 (F, S, S, 3) on the device; out may be `restored` itself (any other overlap of out with an input is VSP_EINVAL).  Integer
+ * arithmetic only, per face and channel, shifts arithmetic, // floor division:
+ *
+ *   validity  pixel (x, y) of face i is valid iff the centre cell of its crop tables lies inside its photo:
+ *                 0 <= (cx[y] + ax[x]) >> 10 < w  and  0 <= (cy[y] + bx[x]) >> 10 < h      (items[i], vsp_face_crop_u8's tables)
+ *             -- the same rule for the bilinear and the anti-aliased crop.  items == tables == NULL: every pixel is valid.
+ *   VSP_COLOR_FIX_WAVELET (levels L = 1 .. VSP_COLOR_FIX_MAX_LEVELS)
+ *                 d = valid ? (c - r) 64 : 0
+ *                 for l = 0 .. L - 1, s = 2^l, indices clamped to [0, S - 1]:
+ *                     d = (d[x - s] + 2 d[x] + d[x + s] + 2) >> 2 along x over the whole plane, then the same along y
+ *                 out = clamp(r + ((d + 32) >> 6), 0, 255)
+ *   VSP_COLOR_FIX_STATS   N valid pixels, sums over them, 64-bit:  S1c = sum c, S2c = sum c^2, S1r, S2r likewise
+ *                 vc = ((N S2c - S1c^2) 256) // N^2,  vr likewise;  g = clamp(isqrt((vc << 24) // max(vr, 1)), 1024, 16384)
+ *                 mc = (S1c 256 + N // 2) // N,  mr likewise;  out = clamp((g (r 256 - mr) + mc 4096 + 2^19) >> 20, 0, 255)
+ *                 N = 0: out = r.  `levels` is checked and otherwise unused.  S above VSP_COLOR_FIX_STATS_MAX_SIDE: VSP_ENOTSUP
+ *                 (the 64-bit products above hold up to there).
+ *
+ * scratch: device memory, 16-byte aligned, that the call may overwrite: 12 F S^2 bytes for the wavelet (two int16 (F, 3, S, S)
+ * planes), 128 F bytes for the statistics (sixteen 64-bit sums per face, zeroed by the call).  Nothing is copied to the host.
+ * `items` / `tables` are read on the host for the checks, `items_dev` / `tables_dev` are the same data in device memory.
+ * VSP_EINVAL, nothing launched: a null pointer, F < 0, S < 1 or above VSP_FACE_MAX_SIDE, levels outside 1 .. 6, an unknown mode, a
+ * buffer of 2 GiB or more, a scratch too small or misaligned, only some of the four item / table pointers given, an item whose table
+ * extents are not S x S, whose photo size is not positive or whose tables leave `tables`, a table entry of magnitude 2^30 or more.
+ * F = 0 returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_COLOR_FIX_STATS 0
+#define VSP_COLOR_FIX_WAVELET 1
+#define VSP_COLOR_FIX_MAX_LEVELS 6
+#define VSP_COLOR_FIX_STATS_MAX_SIDE 1024
+
+int vsp_color_fix_u8(const uint8_t* crop, const uint8_t* restored, uint8_t* out, int F, int S, int mode, int levels,
+                     const vsp_face_item* items, const vsp_face_item* items_dev, const int32_t* tables, const int32_t* tables_dev,
+                     size_t table_ints, void* scratch, size_t scratch_bytes, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,14 @@
              face's crop and the first photo's paste are compared with tests/photo_aa_ref.py on the host.
 
     python tools/bench_photo.py --antialias [--out profiles/photo_aa_bench.json]
+
+  --color_fix MODE   instead: the colour fix (vsp_color_fix_u8; MODE stats, wavelet or both) on the 16 crops of the `kernels`
+             workload at upscale 1, beside the crop and the paste of the same run, median of 30; the NumPy restatement
+             (tests/color_fix_ref.py) on the host, timed once (its integer elementwise operations run on the calling thread), and
+             whether the bytes are equal; the bytes each mode must move -- every buffer counted once, halo re-reads not counted, so
+             `effective_gb_per_s` is a floor of the traffic, not a bandwidth measurement.
+
+    python tools/bench_photo.py --color_fix both [--out profiles/color_fix_bench.json]
 """
 import argparse
 import json
@@ -137,6 +145,44 @@ def bench_antialias(face_px):
     return res
 
 
+def bench_color_fix(photos, marks, modes, levels=5):
+    import color_fix_ref as CF
+    from vspbfr_amd import photo as P
+    faces = [(k, pts) for k, per in enumerate(marks) for pts in per]
+    plan = P.FacePlan(photos, faces, size=512)
+    plan.upload("cuda")
+    crops = P.crop_faces(plan, "cuda")[0]
+    c = crops.cpu().numpy()
+    rng = np.random.default_rng(1)
+    restored = np.clip(np.rint(0.7 * c.astype(np.float64) + 40 + rng.normal(0, 8, c.shape)), 0, 255).astype(np.uint8)   # a tone shift plus noise
+    rdev = torch.from_numpy(restored).cuda()
+    out = plan.background("cuda")
+    fixed = torch.empty_like(rdev)
+    res = {"faces": plan.n, "S": 512, "levels": levels}
+    res["crop_u8_f32"] = events(lambda: P.crop_faces(plan, "cuda", u8=True, f32=True))
+    res["paste"] = events(lambda: P.paste_faces(plan, rdev, "cuda", out=out))
+    valid = [CF.validity_from_landmarks(pts, 512, photos[k].shape[1], photos[k].shape[0]) for k, pts in faces]
+    res["valid_share"] = round(float(np.mean([v.mean() for v in valid])), 4)
+    u8 = plan.n * 512 * 512 * 3
+    # wavelet: first level reads c and r and writes an int16 plane, the levels between read and write one, the last reads one and r and
+    # writes uint8; stats: the reduction reads c and r, the apply reads r and writes uint8
+    moved = {"wavelet": u8 * (2 + 2) + (levels - 2) * 4 * u8 + u8 * (2 + 1 + 1), "stats": 4 * u8}
+    for mode in modes:
+        r = events(lambda: P.color_fix(crops, rdev, mode, plan=plan, device="cuda", levels=levels, out=fixed))
+        r["bytes_moved_mb"] = round(moved[mode] / 1e6, 1)       # each buffer once: halo re-reads are not counted
+        r["effective_gb_per_s"] = round(moved[mode] / 1e6 / r["median_ms"], 1)
+        r["ratio_to_crop"] = round(r["median_ms"] / res["crop_u8_f32"]["median_ms"], 2)
+        r["ratio_to_paste"] = round(r["median_ms"] / res["paste"]["median_ms"], 2)
+        t0 = time.perf_counter()
+        ref = CF.fix_batch(c, restored, mode, valid, levels)
+        r["host_numpy_ms"] = round((time.perf_counter() - t0) * 1000, 1)
+        got = P.color_fix(crops, rdev, mode, plan=plan, device="cuda", levels=levels).cpu().numpy()
+        r["bytes_equal_host"] = bool(np.array_equal(got, ref))
+        r["bytes_moved_by_the_fix_share"] = round(float((ref != restored).mean()), 4)
+        res[mode] = r
+    return res
+
+
 def bench_cli(tmp, photos, marks):
     from PIL import Image
     from vspbfr_amd import restore_photos as RP
@@ -189,9 +235,21 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--skip-cli", action="store_true")
     ap.add_argument("--antialias", action="store_true", help="the anti-aliased kernels against the bilinear ones at three face sizes")
+    ap.add_argument("--color_fix", choices=["stats", "wavelet", "both"], default=None, help="the colour fix beside crop and paste")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_photo: no GPU")
+    if a.color_fix:
+        photos, marks = workload()
+        res = {"what": "16 faces from 8 photos of 1024 x 1536 (w x h), S = 512, upscale 1: colour fix (DESIGN 17) beside crop and paste; HIP "
+                       "events, median of 30", "pipeline_step_ms": PIPELINE_STEP_MS, "cpus_used": len(os.sched_getaffinity(0))}
+        res.update(bench_color_fix(photos, marks, ["wavelet", "stats"] if a.color_fix == "both" else [a.color_fix]))
+        line = json.dumps(res, indent=1)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.antialias:
         res = {"what": "16 faces from 8 photos, S = 512, upscale 1: filtered (DESIGN 16) against bilinear kernels; HIP events, median of 30",
                "pipeline_step_ms": PIPELINE_STEP_MS, "cpus_used": len(os.sched_getaffinity(0)),

@@ -198,6 +198,7 @@ SIGNATURES = {
     "vsp_face_crop_aa_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
     "vsp_face_paste_aa_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p,
                              C.c_size_t, _p, _p, _i, _p],
+    "vsp_color_fix_u8": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],

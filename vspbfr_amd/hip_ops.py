@@ -1803,6 +1803,44 @@ def face_paste_aa_u8(plan, photos, crops, items, tables, fwd, tiles, tile_faces,
     return photos
 
 
+COLOR_FIX_MODES = {"stats": 0, "wavelet": 1}      # include/vspbfr_hip.h VSP_COLOR_FIX_STATS / VSP_COLOR_FIX_WAVELET
+
+
+def color_fix_u8(crops, restored, mode, plan=None, items=None, tables=None, levels=5, out=None):
+    """The colour fix of DESIGN 17 (vsp_color_fix_u8, csrc/color_fix.hip) on two (F, S, S, 3) uint8 device tensors: mode "wavelet" keeps the
+    restored high frequencies and takes the low ones (`levels` dilated [1 2 1] blurs) from the crop, "stats" moves the restored crop's
+    per-channel mean and deviation onto the crop's.  plan / items / tables: a FacePlan and its crop_items / crop_tables sections on the
+    device -- pixels whose centre cell lies outside the photo take no part; all None: every pixel is valid.  out: None (a new tensor)
+    or a contiguous tensor like `restored`, which may be `restored` itself.  The scratch is allocated here.  Returns out."""
+    import ctypes as Ct
+    _u8(crops, "crops"), _u8(restored, "restored")
+    if mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color_fix_u8: mode {mode!r} (one of {sorted(COLOR_FIX_MODES)})")
+    if crops.dim() != 4 or crops.shape[3] != 3 or crops.shape[1] != crops.shape[2] or crops.shape != restored.shape:
+        raise RuntimeError(f"color_fix_u8: crops {tuple(crops.shape)} and restored {tuple(restored.shape)} must both be (F, S, S, 3)")
+    F, S = int(crops.shape[0]), int(crops.shape[1])
+    if out is None:
+        out = torch.empty_like(restored)
+    _u8(out, "out")
+    if out.shape != restored.shape:
+        raise RuntimeError("color_fix_u8: out must have the shape of restored")
+    if (plan is None) != (items is None) or (plan is None) != (tables is None):
+        raise RuntimeError("color_fix_u8: plan, items and tables go together")
+    host_items = host_tables = dev_items = dev_tables = None
+    table_ints = 0
+    if plan is not None:
+        _u8(items, "items"), _u8(tables, "tables")
+        if plan.n != F or plan.S != S or items.numel() != F * Ct.sizeof(_lib.FaceItem) or tables.numel() != plan.crop_tables.nbytes:
+            raise RuntimeError("color_fix_u8: the plan or its device sections do not match the crops")
+        host_items, host_tables = Ct.cast(plan.crop_items, Ct.c_void_p), plan.crop_tables.ctypes.data_as(Ct.c_void_p)
+        dev_items, dev_tables, table_ints = _ptr(items), _ptr(tables), plan.crop_tables.size
+    nbytes = 12 * F * S * S if mode == "wavelet" else 128 * F
+    scratch = torch.empty(max(nbytes, 16), device=restored.device, dtype=torch.uint8)
+    check(lib.vsp_color_fix_u8(_ptr(crops), _ptr(restored), _ptr(out), F, S, COLOR_FIX_MODES[mode], int(levels), host_items, dev_items,
+                               host_tables, dev_tables, table_ints, _ptr(scratch), nbytes, _stream()), "color_fix_u8")
+    return out
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types

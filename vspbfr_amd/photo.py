@@ -6,6 +6,8 @@
                                 tile tables, the packed photo bytes -- the counterpart of resample.ResamplePlan
     crop_faces / paste_faces    vsp_face_crop_u8 / vsp_face_paste_u8 on a plan (the *_aa entries for a plan built with antialias=True:
                                 a face that is minified is resampled by a tent filter one destination pixel wide)
+    color_fix                   vsp_color_fix_u8 on the crops and the restored crops: the restored faces take their colours back from the
+                                photo before the paste, "stats" or "wavelet"
     PhotoRestorer               photos + landmarks -> photos with their faces restored by a RestorationPipeline
 
 All device arithmetic is integer: the float64 geometry ends in the tables built here (`face_tables`), which tests/photo_ref.py restates.
@@ -406,23 +408,56 @@ def paste_faces(plan, restored_u8, device, ramp=None, out=None):
     return out
 
 
+COLOR_FIX_MODES = ("stats", "wavelet")
+MAX_COLOR_LEVELS = 6           # VSP_COLOR_FIX_MAX_LEVELS
+
+
+def check_color_fix(mode, levels=5):
+    """(mode or None, levels) of a colour-fix request, ValueError for an unknown mode or levels outside 1..6; None and "none" ask for none"""
+    mode = None if mode in (None, "none") else mode
+    if mode is not None and mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color_fix: mode {mode!r} (None, 'stats' or 'wavelet')")
+    if isinstance(levels, bool) or int(levels) != levels or not 1 <= int(levels) <= MAX_COLOR_LEVELS:
+        raise ValueError(f"color_fix: levels {levels!r} (1..{MAX_COLOR_LEVELS})")
+    return mode, int(levels)
+
+
+def color_fix(crops_u8, restored_u8, mode, plan=None, device=None, levels=5, out=None):
+    """The colour fix of DESIGN 17 on any pair of (F, S, S, 3) uint8 device tensors -> (F, S, S, 3) uint8 (`out`, which may be restored_u8
+    itself; default a new tensor).  mode "wavelet": the restored crop keeps its own high frequencies and takes the low ones -- `levels`
+    dilated [1 2 1] blurs of the difference -- from the crop; "stats": its per-channel mean and deviation move onto the crop's.  `plan`
+    (a FacePlan whose faces these crops are) supplies validity: crop pixels whose centre cell lies outside the photo hold the border
+    colour and take no part.  Without a plan every pixel is valid.  device: where the plan's tables go (default: the crops' device)."""
+    from . import hip_ops
+    mode, levels = check_color_fix(mode, levels)
+    if mode is None:
+        raise ValueError("color_fix: mode None (nothing to do)")
+    if plan is None:
+        return hip_ops.color_fix_u8(crops_u8, restored_u8, mode, levels=levels, out=out)
+    dev = plan.upload(crops_u8.device if device is None else device)
+    return hip_ops.color_fix_u8(crops_u8, restored_u8, mode, plan, dev["crop_items"], dev["crop_tables"], levels=levels, out=out)
+
+
 class PhotoRestorer:
     """photos + five-point landmarks -> the photos with every face restored.  The photos stay on the device: crop (vsp_face_crop_u8),
     `pipe` (a RestorationPipeline) over the faces of all photos in batches of `batch`, quantisation to uint8 as PngWriter does
     (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4.
-    antialias=True: the anti-aliased entries for crop and paste."""
+    antialias=True: the anti-aliased entries for crop and paste.  color_fix="stats" or "wavelet": the restored crops take
+    their colours back from the crops (vsp_color_fix_u8) and the fixed crops are pasted."""
 
     def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER,
-                 antialias=False):
+                 antialias=False, color_fix=None, color_levels=5):
         if int(upscale) not in (1, 2, 4) or int(batch) < 1:
             raise ValueError(f"PhotoRestorer: batch {batch}, upscale {upscale}")
         self.pipe, self.batch, self.upscale, self.size, self.border = pipe, int(batch), int(upscale), int(size), tuple(border)
         self.antialias = bool(antialias)       # minified faces through the tent filter of DESIGN 16, crop and paste
         self.ramp = default_ramp(inset, feather)
+        self.color_fix, self.color_levels = check_color_fix(color_fix, color_levels)
 
     def __call__(self, photos, landmarks, device, names=None):
         """photos: uint8 (h, w, 3) arrays; landmarks: per photo a list of (5, 2) point sets (None or [] for none) ->
-        (output photos: device uint8 (upscale h, upscale w, 3) tensors, crops (F, S, S, 3) uint8, restored (F, S, S, 3) uint8, plan)"""
+        (output photos: device uint8 (upscale h, upscale w, 3) tensors, crops (F, S, S, 3) uint8, restored (F, S, S, 3) uint8, plan);
+        with a colour fix a fifth element, the fixed crops (F, S, S, 3) uint8 that were pasted (`restored` stays the network's output)"""
         import torch
 
         from . import hip_ops
@@ -431,7 +466,8 @@ class PhotoRestorer:
         S = self.size
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)
-            return plan.split(plan.background(device)), empty, empty, plan
+            head = (plan.split(plan.background(device)), empty, empty, plan)
+            return head if self.color_fix is None else head + (empty,)
         crops, low = crop_faces(plan, device, u8=True, f32=True, border=self.border)
         restored = []
         with torch.no_grad():
@@ -439,5 +475,9 @@ class PhotoRestorer:
                 out = self.pipe(low[i:i + self.batch])
                 restored.append(hip_ops.quantize_u8_nhwc(out["restored"].contiguous(), -1.0, 1.0))
         restored = torch.cat(restored) if len(restored) > 1 else restored[0]
-        out = paste_faces(plan, restored, device, self.ramp)
-        return plan.split(out), crops, restored, plan
+        if self.color_fix is None:
+            out = paste_faces(plan, restored, device, self.ramp)
+            return plan.split(out), crops, restored, plan
+        fixed = color_fix(crops, restored, self.color_fix, plan, device, self.color_levels)
+        out = paste_faces(plan, fixed, device, self.ramp)
+        return plan.split(out), crops, restored, plan, fixed

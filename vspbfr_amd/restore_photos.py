@@ -1,7 +1,7 @@
 """Restore the faces inside whole photos and give the photos back.
 
     python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
-        [--inset PX] [--feather PX] [--antialias] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
@@ -21,6 +21,12 @@ through (resized if asked) -- with --save_faces also <stem>_<k>_crop.png and <st
 tent filter one destination pixel wide instead of four bilinear taps; report.json then lists per face `crop_minify` and
 `paste_minify`.  A minification above 16 is refused while the landmarks are validated.
 
+--color_fix stats | wavelet: before the paste the restored crop takes its colours back from the crop (vspbfr_amd.photo.color_fix,
+csrc/color_fix.hip) -- `stats` moves its per-channel mean and deviation onto the crop's, `wavelet` keeps its high frequencies
+and takes the low ones (--color_levels dilated blurs, default 5, 1..6) from the crop; crop pixels outside the photo take no part.  The
+fixed crop is what is pasted; with --save_faces it is written as <stem>_<k>_fixed.png beside _crop.png and _restore.png, which stay the
+crop and the network's output.  report.json then lists `color_fix` and `color_levels`.  Default none: nothing changes.
+
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
 import argparse
@@ -32,7 +38,7 @@ import torch
 
 from .e4e import E4e_embedding
 from .imageio import PngWriter, list_images
-from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, check_minify, similarity_from_landmarks
+from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, check_color_fix, check_minify, similarity_from_landmarks
 from .pipeline import RestorationPipeline, load_ddpm, shard_range
 from .restorenet import Restoration_net
 
@@ -93,7 +99,7 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
     for group in _groups(names[lo:hi], landmarks, args.batch):
         photos = [_decode(os.path.join(args.photos, n)) for n in group]
-        outs, crops, restored, plan = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
+        outs, crops, restored, plan, *fixed = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
         for k, n in enumerate(group):
             stem = os.path.join(args.out, os.path.splitext(n)[0])
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
@@ -103,6 +109,8 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
                 for j, i in enumerate(mine):
                     writer.submit(crops[i:i + 1], [f"{stem}_{j}_crop.png"])
                     writer.submit(restored[i:i + 1], [f"{stem}_{j}_restore.png"])
+                    if fixed:
+                        writer.submit(fixed[0][i:i + 1], [f"{stem}_{j}_fixed.png"])
             report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ".png", args.out),
                            "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
             if plan.antialias:
@@ -110,8 +118,11 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
                 report[-1]["paste_minify"] = [round(plan.paste_minify[i], 6) for i in mine]
     writer.drain()
     name = "report.json" if world == 1 else "report_%d.json" % rank
+    head = {"upscale": args.upscale, "crop_size": args.size, "inset": args.inset, "feather": args.feather}
+    if restorer.color_fix is not None:
+        head.update(color_fix=restorer.color_fix, color_levels=restorer.color_levels)
     with open(os.path.join(args.out, name), "w") as f:
-        json.dump({"upscale": args.upscale, "crop_size": args.size, "inset": args.inset, "feather": args.feather, "photos": report}, f, indent=1)
+        json.dump(dict(head, photos=report), f, indent=1)
     return report
 
 
@@ -138,7 +149,15 @@ def main(argv=None):
     ap.add_argument("--feather", type=int, default=DEFAULT_FEATHER, help="px over which the blend rises to the restored face")
     ap.add_argument("--antialias", action="store_true", help="shrink large faces into the crop, and restored crops into small faces, through a "
                                                              "tent filter one destination pixel wide instead of four bilinear taps")
+    ap.add_argument("--color_fix", choices=["none", "stats", "wavelet"], default="none",
+                    help="before the paste the restored crop takes its colours back from the crop: per-channel mean and deviation (stats) "
+                         "or everything below the finest --color_levels wavelet levels (wavelet)")
+    ap.add_argument("--color_levels", type=int, default=5, help="levels of --color_fix wavelet, 1..6")
     args = ap.parse_args(argv)
+    try:                       # the flags are checked before any model is loaded
+        color_fix, color_levels = check_color_fix(args.color_fix, args.color_levels)
+    except ValueError as e:
+        ap.error(str(e))
     if args.batch < 1 or args.inset < 0 or args.feather < 0:
         ap.error("--batch must be at least 1, --inset and --feather at least 0")
     args.latent, args.n_mlp = 512, 8
@@ -167,7 +186,7 @@ def main(argv=None):
     diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
     pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)
     restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather,
-                             antialias=args.antialias)
+                             antialias=args.antialias, color_fix=color_fix, color_levels=color_levels)
     restore_photos(args, restorer, names, landmarks, device, rank, world)
 
 
