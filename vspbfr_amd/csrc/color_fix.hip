@@ -16,14 +16,14 @@
 //
 // Bounds: the entry checks sizes, scratch, items and tables on the host before anything is launched; the kernels index pixels only
 // inside [0, S)^2 of face blockIdx.z / blockIdx.y < F and tables only inside [0, S) of an item's four tables.
-#include "vsp_common.h"
+#include "face_tables.h"
 
 namespace {
 
+using vspface::kTwoGiB;
+
 constexpr int kThreads = 256;
 constexpr int kTW = 64, kTH = 32;          // tile: 16 threads x 4 pixels a row, 16 thread rows x 2 rows
-constexpr int kTableLimit = 1 << 30;
-constexpr uint64_t kTwoGiB = 1ull << 31;
 constexpr int kChunk = kThreads * 16;      // stats: pixels of one workgroup, 4 groups of 4 per thread
 
 struct alignas(8) short4_t {
@@ -455,12 +455,8 @@ int vsp_color_fix_u8(const uint8_t* crop, const uint8_t* restored, uint8_t* out,
       const vsp_face_item& it = items[i];
       VSP_REQUIRE(it.w > 0 && it.h > 0, "color_fix: face %d: photo size %d x %d", i, it.w, it.h);
       VSP_REQUIRE(it.nx == S && it.ny == S, "color_fix: face %d: tables of %d x %d for a crop of side %d", i, it.nx, it.ny, S);
-      VSP_REQUIRE(it.tab_off >= 0 && (uint64_t)it.tab_off + 4ull * (uint64_t)S <= (uint64_t)table_ints,
-                  "color_fix: face %d: tables outside the %zu table entries", i, table_ints);
-      const int32_t* t = tables + it.tab_off;
-      for (int k = 0; k < 4 * S; ++k)
-        VSP_REQUIRE(t[k] > -kTableLimit && t[k] < kTableLimit, "color_fix: face %d: table overflow (entry %d = %d, magnitude 2^30 or more)", i, k,
-                    t[k]);
+      const int rc = vspface::check_tables("color_fix", i, it, tables, table_ints);
+      if (rc != VSP_OK) return rc;
     }
   }
   hipStream_t st = vsp::as_stream(stream);

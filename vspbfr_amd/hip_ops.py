@@ -1717,90 +1717,82 @@ def png_encode(u8, guard=0):
 
 
 # ----------------------------------------------------------------------------------------------- faces inside whole photos
+def _fwd_args(fwd_host, fwd):
+    """the forward tables of a *_aa entry: host pointer, device pointer (both NULL when no face is filtered), entries; () for a plain entry"""
+    import ctypes as Ct
+    if fwd is None:
+        return ()
+    has = fwd_host.size > 0
+    return (fwd_host.ctypes.data_as(Ct.c_void_p) if has else None, _ptr(fwd) if has else None, fwd_host.size)
+
+
+def _face_crop(name, plan, items, tables, fwd, src, border, u8, f32):
+    """face_crop_u8 (fwd None: vsp_face_crop_u8 on the plan's crop_items) and face_crop_aa_u8 (vsp_face_crop_aa_u8 on its crop_aa_items)"""
+    import ctypes as Ct
+    aa = fwd is not None
+    for t, tname in ((items, "items"), (tables, "tables")) + (((fwd, "fwd"),) if aa else ()) + ((src, "src"),):
+        _u8(t, tname)
+    if not (u8 or f32):
+        raise RuntimeError(f"{name}: no output asked for")
+    n, S = plan.n, plan.S
+    entry, host_items = (lib.vsp_face_crop_aa_u8, plan.crop_aa_items) if aa else (lib.vsp_face_crop_u8, plan.crop_items)
+    if (items.numel() != Ct.sizeof(host_items._type_) * n or tables.numel() != plan.crop_tables.nbytes
+            or (aa and fwd.numel() != plan.crop_fwd.nbytes) or src.numel() != plan.src_bytes):
+        raise RuntimeError(f"{name}: the device sections do not have the plan's sizes")
+    out8 = torch.empty((n, S, S, 3), device=src.device, dtype=torch.uint8) if u8 else None
+    outf = torch.empty((n, 3, S, S), device=src.device, dtype=torch.float32) if f32 else None
+    check(entry(_ptr(out8), _ptr(outf), _ptr(src), plan.src_bytes, plan.crop_tables.ctypes.data_as(Ct.c_void_p), _ptr(tables),
+                plan.crop_tables.size, *_fwd_args(plan.crop_fwd if aa else None, fwd), Ct.cast(host_items, Ct.c_void_p), _ptr(items), n, S,
+                int(border[0]), int(border[1]), int(border[2]), _stream()), name)
+    return out8, outf
+
+
+def _face_paste(name, plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev):
+    """face_paste_u8 (fwd None: vsp_face_paste_u8 on the plan's paste_items) and face_paste_aa_u8 (vsp_face_paste_aa_u8 on its paste_aa_items)"""
+    import ctypes as Ct
+    aa = fwd is not None
+    for t, tname in ((photos, "photos"), (crops, "crops"), (items, "items"), (tables, "tables")) + (((fwd, "fwd"),) if aa else ()) + (
+            (tiles, "tiles"), (tile_faces, "tile_faces")):
+        _u8(t, tname)
+    n, S = plan.n, plan.S
+    if not isinstance(ramp_dev, torch.Tensor) or not ramp_dev.is_cuda or ramp_dev.dtype != torch.int16 or ramp_dev.numel() != ramp.size:
+        raise RuntimeError(f"{name}: ramp_dev must be the ramp as a CUDA int16 tensor")
+    entry, host_items = (lib.vsp_face_paste_aa_u8, plan.paste_aa_items) if aa else (lib.vsp_face_paste_u8, plan.paste_items)
+    if (photos.numel() != plan.out_bytes or crops.numel() != n * S * S * 3 or items.numel() != Ct.sizeof(host_items._type_) * n
+            or tables.numel() != plan.paste_tables.nbytes or (aa and fwd.numel() != plan.paste_fwd.nbytes)
+            or tiles.numel() != plan.ntiles * Ct.sizeof(_lib.FaceTile) or tile_faces.numel() != plan.tile_faces.nbytes):
+        raise RuntimeError(f"{name}: the device buffers do not have the plan's sizes")
+    check(entry(_ptr(photos), plan.out_bytes, _ptr(crops), crops.numel(), plan.paste_tables.ctypes.data_as(Ct.c_void_p), _ptr(tables),
+                plan.paste_tables.size, *_fwd_args(plan.paste_fwd if aa else None, fwd), Ct.cast(host_items, Ct.c_void_p), _ptr(items), n, S,
+                Ct.cast(plan.tiles, Ct.c_void_p), _ptr(tiles), plan.ntiles, plan.tile_faces.ctypes.data_as(Ct.c_void_p), _ptr(tile_faces),
+                plan.tile_faces.size, ramp.ctypes.data_as(Ct.c_void_p), _ptr(ramp_dev), int(ramp.size), _stream()), name)
+    return photos
+
+
 def face_crop_u8(plan, items, tables, src, border=(128, 128, 128), u8=True, f32=False):
     """The aligned S x S crop of every face of a vspbfr_amd.photo.FacePlan (vsp_face_crop_u8, csrc/face_warp.hip).  `items`, `tables`, `src`:
     the plan's crop_items / crop_tables / photos sections on the device (FacePlan.upload).  The library checks the plan's HOST tables
     before it launches.  Returns (u8 (F, S, S, 3) uint8 or None, f32 (F, 3, S, S) fp32 or None) on the current stream."""
-    import ctypes as Ct
-    _u8(items, "items"), _u8(tables, "tables"), _u8(src, "src")
-    if not (u8 or f32):
-        raise RuntimeError("face_crop_u8: no output asked for")
-    n, S = plan.n, plan.S
-    if items.numel() != n * Ct.sizeof(_lib.FaceItem) or tables.numel() != plan.crop_tables.nbytes or src.numel() != plan.src_bytes:
-        raise RuntimeError("face_crop_u8: the device sections do not have the plan's sizes")
-    out8 = torch.empty((n, S, S, 3), device=src.device, dtype=torch.uint8) if u8 else None
-    outf = torch.empty((n, 3, S, S), device=src.device, dtype=torch.float32) if f32 else None
-    check(lib.vsp_face_crop_u8(_ptr(out8), _ptr(outf), _ptr(src), plan.src_bytes, plan.crop_tables.ctypes.data_as(Ct.c_void_p), _ptr(tables),
-                               plan.crop_tables.size, Ct.cast(plan.crop_items, Ct.c_void_p), _ptr(items), n, S, int(border[0]),
-                               int(border[1]), int(border[2]), _stream()), "face_crop_u8")
-    return out8, outf
+    return _face_crop("face_crop_u8", plan, items, tables, None, src, border, u8, f32)
 
 
 def face_paste_u8(plan, photos, crops, items, tables, tiles, tile_faces, ramp, ramp_dev):
     """Paste the restored crops ((F, S, S, 3) uint8) into the packed output photos, in place (vsp_face_paste_u8, csrc/face_warp.hip).
     `items`, `tables`, `tiles`, `tile_faces`: the plan's paste sections on the device; ramp: host uint16 array, ramp_dev: the same
     values on the device (int16 storage).  Returns photos."""
-    import ctypes as Ct
-    for t, name in ((photos, "photos"), (crops, "crops"), (items, "items"), (tables, "tables"), (tiles, "tiles"), (tile_faces, "tile_faces")):
-        _u8(t, name)
-    n, S = plan.n, plan.S
-    if not isinstance(ramp_dev, torch.Tensor) or not ramp_dev.is_cuda or ramp_dev.dtype != torch.int16 or ramp_dev.numel() != ramp.size:
-        raise RuntimeError("face_paste_u8: ramp_dev must be the ramp as a CUDA int16 tensor")
-    if (photos.numel() != plan.out_bytes or crops.numel() != n * S * S * 3 or items.numel() != n * Ct.sizeof(_lib.FaceItem)
-            or tables.numel() != plan.paste_tables.nbytes or tiles.numel() != plan.ntiles * Ct.sizeof(_lib.FaceTile)
-            or tile_faces.numel() != plan.tile_faces.nbytes):
-        raise RuntimeError("face_paste_u8: the device buffers do not have the plan's sizes")
-    check(lib.vsp_face_paste_u8(_ptr(photos), plan.out_bytes, _ptr(crops), crops.numel(), plan.paste_tables.ctypes.data_as(Ct.c_void_p),
-                                _ptr(tables), plan.paste_tables.size, Ct.cast(plan.paste_items, Ct.c_void_p), _ptr(items), n, S,
-                                Ct.cast(plan.tiles, Ct.c_void_p), _ptr(tiles), plan.ntiles, plan.tile_faces.ctypes.data_as(Ct.c_void_p),
-                                _ptr(tile_faces), plan.tile_faces.size, ramp.ctypes.data_as(Ct.c_void_p), _ptr(ramp_dev), int(ramp.size),
-                                _stream()), "face_paste_u8")
-    return photos
+    return _face_paste("face_paste_u8", plan, photos, crops, items, tables, None, tiles, tile_faces, ramp, ramp_dev)
 
 
 def face_crop_aa_u8(plan, items, tables, fwd, src, border=(128, 128, 128), u8=True, f32=False):
     """face_crop_u8 for a FacePlan built with antialias=True (vsp_face_crop_aa_u8): `items` is the plan's crop_aa_items section and `fwd`
     its crop_fwd section; a face with reach > 0 is resampled by the tent filter of DESIGN 16, the others exactly as face_crop_u8 does."""
-    import ctypes as Ct
-    _u8(items, "items"), _u8(tables, "tables"), _u8(fwd, "fwd"), _u8(src, "src")
-    if not (u8 or f32):
-        raise RuntimeError("face_crop_aa_u8: no output asked for")
-    n, S = plan.n, plan.S
-    if (items.numel() != n * Ct.sizeof(_lib.FaceAAItem) or tables.numel() != plan.crop_tables.nbytes or fwd.numel() != plan.crop_fwd.nbytes
-            or src.numel() != plan.src_bytes):
-        raise RuntimeError("face_crop_aa_u8: the device sections do not have the plan's sizes")
-    out8 = torch.empty((n, S, S, 3), device=src.device, dtype=torch.uint8) if u8 else None
-    outf = torch.empty((n, 3, S, S), device=src.device, dtype=torch.float32) if f32 else None
-    has = plan.crop_fwd.size > 0
-    check(lib.vsp_face_crop_aa_u8(_ptr(out8), _ptr(outf), _ptr(src), plan.src_bytes, plan.crop_tables.ctypes.data_as(Ct.c_void_p), _ptr(tables),
-                                  plan.crop_tables.size, plan.crop_fwd.ctypes.data_as(Ct.c_void_p) if has else None, _ptr(fwd) if has else None,
-                                  plan.crop_fwd.size, Ct.cast(plan.crop_aa_items, Ct.c_void_p), _ptr(items), n, S, int(border[0]),
-                                  int(border[1]), int(border[2]), _stream()), "face_crop_aa_u8")
-    return out8, outf
+    return _face_crop("face_crop_aa_u8", plan, items, tables, fwd, src, border, u8, f32)
 
 
 def face_paste_aa_u8(plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev):
     """face_paste_u8 for a FacePlan built with antialias=True (vsp_face_paste_aa_u8): `items` is the plan's paste_aa_items section and
     `fwd` its paste_fwd section.  Returns photos."""
-    import ctypes as Ct
-    for t, name in ((photos, "photos"), (crops, "crops"), (items, "items"), (tables, "tables"), (fwd, "fwd"), (tiles, "tiles"),
-                    (tile_faces, "tile_faces")):
-        _u8(t, name)
-    n, S = plan.n, plan.S
-    if not isinstance(ramp_dev, torch.Tensor) or not ramp_dev.is_cuda or ramp_dev.dtype != torch.int16 or ramp_dev.numel() != ramp.size:
-        raise RuntimeError("face_paste_aa_u8: ramp_dev must be the ramp as a CUDA int16 tensor")
-    if (photos.numel() != plan.out_bytes or crops.numel() != n * S * S * 3 or items.numel() != n * Ct.sizeof(_lib.FaceAAItem)
-            or tables.numel() != plan.paste_tables.nbytes or fwd.numel() != plan.paste_fwd.nbytes
-            or tiles.numel() != plan.ntiles * Ct.sizeof(_lib.FaceTile) or tile_faces.numel() != plan.tile_faces.nbytes):
-        raise RuntimeError("face_paste_aa_u8: the device buffers do not have the plan's sizes")
-    has = plan.paste_fwd.size > 0
-    check(lib.vsp_face_paste_aa_u8(_ptr(photos), plan.out_bytes, _ptr(crops), crops.numel(), plan.paste_tables.ctypes.data_as(Ct.c_void_p),
-                                   _ptr(tables), plan.paste_tables.size, plan.paste_fwd.ctypes.data_as(Ct.c_void_p) if has else None,
-                                   _ptr(fwd) if has else None, plan.paste_fwd.size, Ct.cast(plan.paste_aa_items, Ct.c_void_p), _ptr(items), n, S,
-                                   Ct.cast(plan.tiles, Ct.c_void_p), _ptr(tiles), plan.ntiles, plan.tile_faces.ctypes.data_as(Ct.c_void_p),
-                                   _ptr(tile_faces), plan.tile_faces.size, ramp.ctypes.data_as(Ct.c_void_p), _ptr(ramp_dev), int(ramp.size),
-                                   _stream()), "face_paste_aa_u8")
-    return photos
+    return _face_paste("face_paste_aa_u8", plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev)
 
 
 COLOR_FIX_MODES = {"stats": 0, "wavelet": 1}      # include/vspbfr_hip.h VSP_COLOR_FIX_STATS / VSP_COLOR_FIX_WAVELET
