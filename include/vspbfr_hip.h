@@ -41,7 +41,7 @@ const char* vsp_last_error(void);
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
- * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item): lets a binding in
+ * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -967,6 +967,55 @@ int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* cro
 int vsp_color_fix_u8(const uint8_t* crop, const uint8_t* restored, uint8_t* out, int F, int S, int mode, int levels,
                      const vsp_face_item* items, const vsp_face_item* items_dev, const int32_t* tables, const int32_t* tables_dev,
                      size_t table_ints, void* scratch, size_t scratch_bytes, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device-side JPEG encoder: the entropy-coded segments of a ragged batch of packed RGB uint8 images (csrc/jpeg.hip).
+ * Baseline sequential DCT, 8 bits, YCbCr, 4:4:4 or 4:2:0, the Annex K quantisation tables scaled by `quality` as libjpeg's
+ * jpeg_set_quality(q, TRUE) scales them, the Annex K Huffman tables, a restart interval of `restart` MCUs.  The host frames the file
+ * (vspbfr_amd/jpeg.py assemble: SOI, JFIF APP0, 2 DQT, SOF0, 4 DHT, DRI, SOS, the segment, EOI); tests/jpeg_ref.py restates every
+ * step in NumPy and the files equal Pillow's save(quality, subsampling, restart_marker_blocks = restart) byte for byte.
+ *
+ *   pixels     jccolor's 16-bit fixed point RGB -> YCbCr; 4:2:0 chroma = h2v2 box with the alternating 1 / 2 bias; columns and rows
+ *              past the image repeat the last one, a chroma row past the last downsampled row repeats that row (csrc/jpeg_common.h)
+ *   blocks     ISLOW forward DCT, quantised by round-half-away(c / (8 q)).  4:2:0 MCU = 16 x 16 pixels: Y00 Y01 Y10 Y11 Cb Cr; a luma
+ *              block that starts past ceil(w / 8) columns or ceil(h / 8) rows is a dummy as the compressor makes it: AC zero, DC that
+ *              of the previous block of the MCU.  4:4:4 MCU = 8 x 8 pixels: Y Cb Cr
+ *   intervals  image i has M = MCUs across x down, ceil(M / restart) intervals; interval k codes the MCUs k restart .. in raster
+ *              order with the DC predictors reset to 0, is padded with 1-bits to a byte, and `FF` bytes are followed by `00`.
+ *              The kernel codes every interval on its own into a slot of `work` (global interval j at byte j * slot, slot =
+ *              vsp_jpeg_interval_bound(min(restart, largest M of the call), subsampling)), then a scan and a gather write image i's
+ *              segment at out + out_off: interval 0, FF D0, interval 1, FF D1, ... the marker number cycling 0..7, none behind the
+ *              last interval.  totals[i] = bytes of that segment (at most vsp_jpeg_image_bound(h, w, restart, subsampling))
+ *   items      given twice: in host memory, checked before anything is launched, and the same table in device memory.  interval0 =
+ *              the number of intervals of the items before it (item 0: 0)
+ *   interval_ws  2 x (intervals of the call) int32 of device memory: byte counts, then offsets
+ * VSP_EINVAL, nothing launched: a null pointer, n outside 0 .. VSP_JPEG_MAX_ITEMS, quality outside 1..100, a subsampling other than
+ * VSP_JPEG_444 / VSP_JPEG_420, restart outside 1..65535, h or w outside 1..65535, an image outside `src`, a segment bound outside
+ * `out`, a wrong interval0, a `work` too small.  VSP_ENOTSUP: src, out or work of 2 GiB or more (the caller encodes on the host).
+ * n = 0 returns VSP_OK.  The bounds return 0 for arguments outside the limits.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_JPEG_444 0            /* Pillow's subsampling numbers */
+#define VSP_JPEG_420 2
+#define VSP_JPEG_MAX_ITEMS 65535
+#define VSP_JPEG_BLOCK_BOUND 416  /* bytes one coded block can take: (22 + 63 x 26) bits, every byte stuffed */
+
+typedef struct vsp_jpeg_item {
+  int64_t src_off;     /* byte offset of the (h, w, 3) image in `src`, rows of 3 w bytes without padding */
+  int64_t out_off;     /* byte offset of its entropy-coded segment in `out` */
+  int32_t h, w;
+  int32_t interval0;   /* index of its first restart interval among all intervals of the call */
+  int32_t pad_;
+} vsp_jpeg_item;
+
+/* restart intervals of one image (0 for arguments outside the limits) */
+int vsp_jpeg_intervals(int h, int w, int restart, int subsampling);
+/* bytes of the slot of an interval of `mcus` MCUs */
+size_t vsp_jpeg_interval_bound(int mcus, int subsampling);
+/* bytes an image's segment can take, markers included */
+size_t vsp_jpeg_image_bound(int h, int w, int restart, int subsampling);
+int vsp_jpeg_encode_u8(uint8_t* out, size_t out_bytes, int32_t* totals, uint8_t* work, size_t work_bytes, int32_t* interval_ws,
+                       const uint8_t* src, size_t src_bytes, const vsp_jpeg_item* items, const vsp_jpeg_item* items_dev, int n,
+                       int quality, int subsampling, int restart, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -183,9 +183,10 @@ def bench_color_fix(photos, marks, modes, levels=5):
     return res
 
 
-def bench_cli(tmp, photos, marks):
+def cli_setup(tmp, photos, marks):
+    """random checkpoints, the photos as PNG files under tmp/photos and a PhotoRestorer at --batch 8 --timesteps 4 --no_sample: what a CLI
+    loop needs besides its args -> (restorer, root, names, landmarks, device); tools/bench_jpeg.py times its loop on the same set-up"""
     from PIL import Image
-    from vspbfr_amd import restore_photos as RP
     from vspbfr_amd.diffusion import Code_diffuser
     from vspbfr_amd.e4e import E4e_embedding, Encoder4Editing, Generator
     from vspbfr_amd.photo import PhotoRestorer
@@ -211,7 +212,12 @@ def bench_cli(tmp, photos, marks):
     g_ema = Restoration_net(512, 512, 8).to(device).eval()
     psp = E4e_embedding(os.path.join(ck, "psp.pt"), out_size=512, size=1024, device=device, use_generator=True)
     pipe = RestorationPipeline(g_ema, psp, load_ddpm(os.path.join(ck, "code_diffuser.pt"), device=device, timesteps=4), mixing=0.5, with_sample=False)
-    restorer = PhotoRestorer(pipe, 8)
+    return PhotoRestorer(pipe, 8), root, names, landmarks, device
+
+
+def bench_cli(tmp, photos, marks):
+    from vspbfr_amd import restore_photos as RP
+    restorer, root, names, landmarks, device = cli_setup(tmp, photos, marks)
     times = {False: [], True: []}
     for rep in range(4):                       # the first of each is the warm run
         for save in (False, True):

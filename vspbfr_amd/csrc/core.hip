@@ -39,6 +39,7 @@ int vsp_struct_size(int which) {
     case 8: return (int)sizeof(vsp_face_item);
     case 9: return (int)sizeof(vsp_face_tile);
     case 10: return (int)sizeof(vsp_face_aa_item);
+    case 11: return (int)sizeof(vsp_jpeg_item);
     default: return -1;
   }
 }

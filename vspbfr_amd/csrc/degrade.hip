@@ -24,8 +24,11 @@
 // Bounds: the Python front end (vspbfr_amd/degrade.py) validates every table entry against the buffers it allocates before the upload;
 // the kernels clamp every index they derive from a table entry as well, so a bad entry can produce wrong pixels but no stray access.
 #include "vsp_common.h"
+#include "jpeg_common.h"
 
 namespace {
+
+using namespace vsp_jpeg;
 
 constexpr int kBlurTile = 64;                        // output tile edge
 constexpr int kBlurRow = 16;                         // outputs per thread (one row)
@@ -229,40 +232,8 @@ __global__ __launch_bounds__(256) void degrade_down_kernel(uint8_t* __restrict__
 
 // ---------------------------------------------------------------------------------------------------------------------- JPEG
 // Integer arithmetic of the Independent JPEG Group's baseline codec as libjpeg / libjpeg-turbo run it by default (ISLOW DCTs,
-// 13-bit constants, 2 extra bits between the passes), written from the algorithm descriptions.
-constexpr int kConstBits = 13, kPass1Bits = 2;
-constexpr int F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633, F1501 = 12299, F1847 = 15137,
-              F1961 = 16069, F2053 = 16819, F2562 = 20995, F3072 = 25172;
-
-__host__ __device__ inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// ISLOW forward DCT of 8 values at stride `s`; pass 1 (rows) keeps PASS1_BITS extra bits, pass 2 (columns) removes them
-// (jfdctint.c).  The outputs are 8x the orthonormal DCT, which the quantiser's divisor absorbs.
-template <bool kPass2>
-__host__ __device__ inline void fdct8(int* d, int s) {
-  const int tmp0 = d[0] + d[7 * s], tmp7 = d[0] - d[7 * s], tmp1 = d[s] + d[6 * s], tmp6 = d[s] - d[6 * s];
-  const int tmp2 = d[2 * s] + d[5 * s], tmp5 = d[2 * s] - d[5 * s], tmp3 = d[3 * s] + d[4 * s], tmp4 = d[3 * s] - d[4 * s];
-  const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-  const int sh = kPass2 ? kConstBits + kPass1Bits : kConstBits - kPass1Bits;
-  if (kPass2) {
-    d[0] = descale(tmp10 + tmp11, kPass1Bits);
-    d[4 * s] = descale(tmp10 - tmp11, kPass1Bits);
-  } else {
-    d[0] = (tmp10 + tmp11) << kPass1Bits;
-    d[4 * s] = (tmp10 - tmp11) << kPass1Bits;
-  }
-  const int z1 = (tmp12 + tmp13) * F0541;
-  d[2 * s] = descale(z1 + tmp13 * F0765, sh);
-  d[6 * s] = descale(z1 - tmp12 * F1847, sh);
-  const int z5 = (tmp4 + tmp5 + tmp6 + tmp7) * F1175;
-  const int a1 = -(tmp4 + tmp7) * F0899, a2 = -(tmp5 + tmp6) * F2562;
-  const int a3 = -(tmp4 + tmp6) * F1961 + z5, a4 = -(tmp5 + tmp7) * F0390 + z5;
-  d[7 * s] = descale(tmp4 * F0298 + a1 + a3, sh);
-  d[5 * s] = descale(tmp5 * F2053 + a2 + a4, sh);
-  d[3 * s] = descale(tmp6 * F3072 + a2 + a3, sh);
-  d[s] = descale(tmp7 * F1501 + a1 + a4, sh);
-}
-
+// 13-bit constants, 2 extra bits between the passes), written from the algorithm descriptions.  The compressor's half is in
+// jpeg_common.h, shared with the file encoder (jpeg.hip); the decoder's half follows.
 // ISLOW inverse DCT of 8 values at stride `s` (jidctint.c).  Pass 1 (columns) leaves PASS1_BITS extra bits; pass 2 (rows) descales by
 // CONST_BITS + PASS1_BITS + 3 and applies the post-IDCT range limit: index (x & 1023) of a table that clamps x + 128 to [0, 255] for
 // |x| < 512 and wraps beyond, exactly as the library's table does.
@@ -292,33 +263,8 @@ __host__ __device__ inline void idct8(int* d, int s) {
   for (int i = 0; i < 8; ++i) d[i * s] = kPass2 ? idct_range_limit(r[i]) : r[i];
 }
 
-// Annex K tables (ITU-T T.81), natural order, scaled like jpeg_set_quality(q, force_baseline = TRUE): 5000 / q below 50, else 200 - 2q
-// percent, (base * scale + 50) / 100 clamped to [1, 255].
-__host__ __device__ inline int jpeg_quant(int q, int chroma, int i) {
-  const unsigned char luma[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,
-                                  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
-                                  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
-                                  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-  const unsigned char chrom[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99,
-                                   99, 99, 47, 66, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-                                   99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-  q = q < 1 ? 1 : q > 100 ? 100 : q;
-  const int scale = q < 50 ? 5000 / q : 200 - 2 * q;
-  const int v = ((chroma ? chrom[i] : luma[i]) * scale + 50) / 100;
-  return v < 1 ? 1 : v > 255 ? 255 : v;
-}
-
-// quantise (round half away from zero of c / (8 q), jcdctmgr.c) and dequantise (jddctmgr.c): what the decoder's IDCT sees
-__host__ __device__ inline int jpeg_requant(int c, int q) {
-  const int d = q << 3;
-  const int k = c < 0 ? -((-c + (d >> 1)) / d) : (c + (d >> 1)) / d;
-  return k * q;
-}
-
-// jccolor.c: 16-bit fixed point, FIX(x) = round(x * 65536); Cb / Cr carry +128 and round with ONE_HALF - 1
-__host__ __device__ inline int rgb_y(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
-__host__ __device__ inline int rgb_cb(int r, int g, int b) { return (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16; }
-__host__ __device__ inline int rgb_cr(int r, int g, int b) { return (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16; }
+// quantise (jpeg_common.h) and dequantise (jddctmgr.c): what the decoder's IDCT sees
+__host__ __device__ inline int jpeg_requant(int c, int q) { return jpeg_quantise(c, q) * q; }
 
 // jdcolor.c: R = Y + round(1.402 (Cr - 128)), B = Y + round(1.772 (Cb - 128)), G = Y + ((-0.34414 (Cb - 128) - 0.71414 (Cr - 128)) in
 // 16-bit fixed point, + ONE_HALF, arithmetic shift), each clamped to [0, 255]
@@ -328,19 +274,6 @@ __host__ __device__ inline void ycc_rgb(int y, int cb, int cr, int& r, int& g, i
   r = clamp255(y + ((91881 * cr + 32768) >> 16));
   g = clamp255(y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
   b = clamp255(y + ((116130 * cb + 32768) >> 16));
-}
-
-struct JpegGeom {
-  int dh, dw, mw, mh, pw, ph, ch, cw;  // image, MCUs across / down, padded size (multiples of 16), real chroma size
-};
-
-__host__ __device__ inline JpegGeom jpeg_geom(int dh, int dw) {
-  JpegGeom g;
-  g.dh = dh, g.dw = dw;
-  g.mw = (dw + 15) / 16, g.mh = (dh + 15) / 16;
-  g.pw = g.mw * 16, g.ph = g.mh * 16;
-  g.cw = (dw + 1) / 2, g.ch = (dh + 1) / 2;
-  return g;
 }
 
 // h2v2 fancy upsampling (jdsample.c): each output takes 9/16, 3/16, 3/16, 1/16 of the four nearest chroma samples; column sums
@@ -378,27 +311,19 @@ __global__ __launch_bounds__(64) void degrade_jpeg_mcu_kernel(uint8_t* __restric
   qt[0][t] = jpeg_quant(it.quality, 0, t);
   qt[1][t] = jpeg_quant(it.quality, 1, t);
   auto px = [&](int c, int y, int x) -> int { return img[c * hw + (int64_t)y * g.dw + x]; };
+  auto rgb = [&](int y, int x, int& R, int& G, int& B) { R = px(2, y, x), G = px(1, y, x), B = px(0, y, x); };
   {  // luma: thread t -> 4 samples of row t / 4
     const int yy = t >> 2;
-    const int y = min(my * 16 + yy, g.dh - 1);
     for (int j = 0; j < 4; ++j) {
-      const int xx = (t & 3) * 4 + j, x = min(mx * 16 + xx, g.dw - 1);
-      blk[(yy >> 3) * 2 + (xx >> 3)][(yy & 7) * 8 + (xx & 7)] = rgb_y(px(2, y, x), px(1, y, x), px(0, y, x)) - 128;
+      const int xx = (t & 3) * 4 + j;
+      blk[(yy >> 3) * 2 + (xx >> 3)][(yy & 7) * 8 + (xx & 7)] = jpeg_luma(g, my * 16 + yy, mx * 16 + xx, rgb) - 128;
     }
   }
   {  // chroma: thread t -> sample t of the 8x8 Cb and Cr blocks
-    const int cy = t >> 3, cx = t & 7;
-    const int gcy = min(my * 8 + cy, g.ch - 1), gcx = mx * 8 + cx;
-    int sb = 0, sr = 0;
-    for (int a = 0; a < 2; ++a)
-      for (int b = 0; b < 2; ++b) {
-        const int y = min(2 * gcy + a, g.dh - 1), x = min(2 * gcx + b, g.dw - 1);
-        const int R = px(2, y, x), G = px(1, y, x), B = px(0, y, x);
-        sb += rgb_cb(R, G, B), sr += rgb_cr(R, G, B);
-      }
-    const int bias = (gcx & 1) ? 2 : 1;
-    blk[4][t] = ((sb + bias) >> 2) - 128;
-    blk[5][t] = ((sr + bias) >> 2) - 128;
+    int cb, cr;
+    jpeg_chroma_h2v2(g, my * 8 + (t >> 3), mx * 8 + (t & 7), rgb, cb, cr);
+    blk[4][t] = cb - 128;
+    blk[5][t] = cr - 128;
   }
   __syncthreads();
   const int b8 = t >> 3, v8 = t & 7;

@@ -1716,6 +1716,71 @@ def png_encode(u8, guard=0):
     return out, seg_bytes, seg_adler, slot
 
 
+JPEG_SUBSAMPLING = {"444": 0, "420": 2}      # include/vspbfr_hip.h VSP_JPEG_444 / VSP_JPEG_420 (Pillow's numbers)
+JPEG_LIMIT_BYTES = 1 << 31                    # a buffer of this size or more: VSP_ENOTSUP
+
+
+def jpeg_layout(sizes, subsampling="420", restart=8):
+    """What one vsp_jpeg_encode_u8 call over packed images of `sizes` = [(h, w), ...] needs: (rows, src_bytes, out_bytes, work_bytes,
+    intervals) -- per image the vsp_jpeg_item fields (src_off, out_off, h, w, interval0), the images back to back in `src` and every
+    segment at a 16-byte boundary of `out`; the three buffer sizes; the number of restart intervals.  None when the entry refuses a size
+    (h or w outside 1..65535).  The one place the Python side works this out: jpeg_encode and jpeg.kernel_serves both ask here."""
+    sub, restart = JPEG_SUBSAMPLING[subsampling], int(restart)
+    mcu = 16 if sub == JPEG_SUBSAMPLING["420"] else 8
+    rows, src, out, total, max_mcus = [], 0, 0, 0, 0
+    for h, w in sizes:
+        h, w = int(h), int(w)
+        nint = lib.vsp_jpeg_intervals(h, w, restart, sub)
+        if nint == 0:
+            return None
+        max_mcus = max(max_mcus, -(-h // mcu) * -(-w // mcu))
+        rows.append((src, out, h, w, total))
+        src, out, total = src + 3 * h * w, out + (lib.vsp_jpeg_image_bound(h, w, restart, sub) + 15) // 16 * 16, total + nint
+    work = total * lib.vsp_jpeg_interval_bound(min(restart, max_mcus), sub) if rows else 0
+    return rows, src, out, work, total
+
+
+def jpeg_encode(buffer, sizes, quality=90, subsampling="420", restart=8):
+    """Entropy-coded JPEG segments of packed RGB images on the current stream (vsp_jpeg_encode_u8, csrc/jpeg.hip).  buffer: 1-D uint8
+    device tensor holding the (h, w, 3) images of `sizes` = [(h, w), ...] back to back.  Returns (out uint8, totals (n,) int32, offsets):
+    image i's segment is out[offsets[i] : offsets[i] + totals[i]]; vspbfr_amd.jpeg.assemble frames it.  Nothing is synchronised: the
+    item table goes up from pinned memory on the current stream, as degrade.py and resample.py send theirs.  Wrong arguments raise
+    RuntimeError (the entry's message); a call that needs a buffer of 2 GiB or more raises NotImplementedError."""
+    import ctypes as Ct
+    from ._lib import JpegItem
+    _u8(buffer, "buffer")
+    if subsampling not in JPEG_SUBSAMPLING:
+        raise RuntimeError(f"jpeg_encode: subsampling {subsampling!r} ('444' or '420')")
+    sub, quality, restart, n = JPEG_SUBSAMPLING[subsampling], int(quality), int(restart), len(sizes)
+    layout = jpeg_layout(sizes, subsampling, restart)
+    if layout is None:
+        raise RuntimeError(f"jpeg_encode: sizes {list(sizes)}, quality {quality}, subsampling {subsampling!r}, restart {restart}")
+    rows, src_bytes, out_bytes, work_bytes, total = layout
+    if buffer.dim() != 1 or buffer.numel() != src_bytes:
+        raise RuntimeError(f"jpeg_encode: a flat buffer of {src_bytes} bytes for these sizes, got {tuple(buffer.shape)}")
+    if n == 0:
+        return torch.empty(0, device=buffer.device, dtype=torch.uint8), torch.empty(0, device=buffer.device, dtype=torch.int32), []
+    if max(src_bytes, out_bytes, work_bytes) >= JPEG_LIMIT_BYTES:
+        raise NotImplementedError(f"jpeg_encode: buffers of {src_bytes}, {out_bytes} and {work_bytes} bytes reach the limit of "
+                                  "vsp_jpeg_encode_u8")
+    dev = buffer.device
+    table = torch.empty(n * Ct.sizeof(JpegItem), dtype=torch.uint8, pin_memory=True)
+    items = (JpegItem * n).from_address(table.data_ptr())
+    for i, row in enumerate(rows):
+        items[i] = JpegItem(*row, 0)
+    out = torch.empty(out_bytes, device=dev, dtype=torch.uint8)
+    work = torch.empty(work_bytes, device=dev, dtype=torch.uint8)
+    ws = torch.empty(2 * total, device=dev, dtype=torch.int32)
+    totals = torch.empty(n, device=dev, dtype=torch.int32)
+    items_dev = table.to(dev, non_blocking=True)
+    rc = lib.vsp_jpeg_encode_u8(_ptr(out), out_bytes, _ptr(totals), _ptr(work), work_bytes, _ptr(ws), _ptr(buffer), src_bytes,
+                                Ct.c_void_p(table.data_ptr()), _ptr(items_dev), n, quality, sub, restart, _stream())
+    if rc == -3:
+        raise NotImplementedError(_lib.last_error())
+    check(rc, "jpeg_encode")
+    return out, totals, [row[1] for row in rows]
+
+
 # ----------------------------------------------------------------------------------------------- faces inside whole photos
 def _fwd_args(fwd_host, fwd):
     """the forward tables of a *_aa entry: host pointer, device pointer (both NULL when no face is filtered), entries; () for a plain entry"""

@@ -12,7 +12,10 @@ host, on a thread pool one batch ahead; the LANCZOS resize, the crop and the nor
 vsp_lanczos_resize_u8) and give the bits `RestoreTestSet.__getitem__` gives.
 
 `PngWriter(encode="device")` is the opt-in device encoder of the other end (`restoration_metrics --encode device`): row filters and deflate run
-on the device (vspbfr_amd.png, vsp_png_encode_u8) and the worker threads only frame and write the files; the pixels are those of the host path."""
+on the device (vspbfr_amd.png, vsp_png_encode_u8) and the worker threads only frame and write the files; the pixels are those of the host path.
+
+`JpegWriter` writes uint8 RGB images as baseline JPEG files (`restore_photos --format jpg`): encode="device" codes them on the device
+(vspbfr_amd.jpeg, vsp_jpeg_encode_u8), encode="host" hands them to Pillow at the same parameters; the two routes write equal bytes."""
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -193,6 +196,61 @@ class PngWriter:
         arr = host.numpy()
         for i, p in enumerate(paths):
             Image.fromarray(arr[i]).save(p)
+
+    @staticmethod
+    def _write(job, paths):
+        for p, data in zip(paths, job.files()):
+            with open(p, "wb") as f:
+                f.write(data)
+
+    def drain(self):
+        for f in self.pending:
+            f.result()
+        self.pending = []
+
+
+class JpegWriter:
+    """Asynchronous JPEG files of uint8 RGB images on the device.  encode="device": colour transform, DCT, quantisation and Huffman
+    coding run on the device (vspbfr_amd.jpeg, csrc/jpeg.hip) and the workers copy the used bytes, frame and write; encode="host":
+    Pillow encodes on the worker threads with the same quality, subsampling and restart interval, which gives the same bytes."""
+
+    def __init__(self, workers=8, quality=90, subsampling="420", restart=None, encode="device"):
+        from . import jpeg
+        if encode not in ("host", "device"):
+            raise ValueError(f"JpegWriter: encode {encode!r}")
+        self.params = jpeg.check_params(quality, subsampling, jpeg.DEFAULT_RESTART if restart is None else restart)
+        self.pool = ThreadPoolExecutor(max_workers=workers)
+        self.pending = []
+        self.encode = encode
+
+    def submit(self, batch, paths):
+        """batch: (B, H, W, 3) uint8 on the device, or (B, 3, H, W) fp32 in [-1, 1], quantised as PngWriter quantises it.  Returns the
+        uint8 device tensor whose pixels the files hold before the lossy coding."""
+        from . import hip_ops as H
+        from . import jpeg
+        u8 = batch if batch.dtype == torch.uint8 else H.quantize_u8_nhwc(batch.contiguous(), -1.0, 1.0)
+        u8 = u8.contiguous()
+        B, Hh, Ww, _ = u8.shape
+        sizes = [(Hh, Ww)] * B
+        if self.encode == "device" and jpeg.kernel_serves(sizes, self.params[1], self.params[2]):
+            job = jpeg.enqueue(u8.reshape(-1), sizes, *self.params)       # kernels + the byte counts' copy on the current stream
+            self.pending.append(self.pool.submit(self._write, job, list(paths)))
+            return u8
+        host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(u8, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.pending.append(self.pool.submit(self._encode, host, ev, list(paths), self.params))
+        return u8
+
+    @staticmethod
+    def _encode(host, ev, paths, params):
+        from . import jpeg
+        ev.synchronize()
+        arr = host.numpy()
+        for i, p in enumerate(paths):
+            with open(p, "wb") as f:
+                f.write(jpeg.pillow_file(arr[i], *params))
 
     @staticmethod
     def _write(job, paths):

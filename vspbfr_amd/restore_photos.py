@@ -1,7 +1,8 @@
 """Restore the faces inside whole photos and give the photos back.
 
     python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
-        [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L]
+        [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
@@ -27,6 +28,12 @@ and takes the low ones (--color_levels dilated blurs, default 5, 1..6) from the 
 fixed crop is what is pasted; with --save_faces it is written as <stem>_<k>_fixed.png beside _crop.png and _restore.png, which stay the
 crop and the network's output.  report.json then lists `color_fix` and `color_levels`.  Default none: nothing changes.
 
+--format jpg: the output photo is OUT/<relative stem>.jpg, a baseline JPEG of --quality (1..100, default 90) and --subsampling (420,
+the default, or 444) with a restart interval of vspbfr_amd.jpeg.DEFAULT_RESTART MCUs.  --encode device (the default of this route)
+codes it on the device (vspbfr_amd.jpeg, csrc/jpeg.hip, DESIGN 18), --encode host hands the pixels to Pillow with the same parameters;
+both write the bytes Pillow writes for the pixels of the png route.  The --save_faces files stay PNG.  report.json then names the .jpg
+files and lists `format`, `quality` and `subsampling`.  Default png: nothing changes.
+
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
 import argparse
@@ -37,7 +44,7 @@ import numpy as np
 import torch
 
 from .e4e import E4e_embedding
-from .imageio import PngWriter, list_images
+from .imageio import JpegWriter, PngWriter, list_images
 from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, check_color_fix, check_minify, similarity_from_landmarks
 from .pipeline import RestorationPipeline, load_ddpm, shard_range
 from .restorenet import Restoration_net
@@ -95,6 +102,9 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
     lo, hi = shard_range(len(names), rank, world)
     os.makedirs(args.out, exist_ok=True)
     writer = PngWriter()
+    jpg = getattr(args, "format", "png") == "jpg"
+    photo_writer = JpegWriter(quality=args.quality, subsampling=args.subsampling, encode=args.encode) if jpg else writer
+    ext = ".jpg" if jpg else ".png"
     report = []
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
     for group in _groups(names[lo:hi], landmarks, args.batch):
@@ -103,7 +113,7 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
         for k, n in enumerate(group):
             stem = os.path.join(args.out, os.path.splitext(n)[0])
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
-            writer.submit(outs[k][None], [stem + ".png"])
+            photo_writer.submit(outs[k][None], [stem + ext])
             mine = [i for i, kk in enumerate(plan.face_photo) if kk == k]
             if args.save_faces:
                 for j, i in enumerate(mine):
@@ -111,16 +121,19 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
                     writer.submit(restored[i:i + 1], [f"{stem}_{j}_restore.png"])
                     if fixed:
                         writer.submit(fixed[0][i:i + 1], [f"{stem}_{j}_fixed.png"])
-            report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ".png", args.out),
+            report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ext, args.out),
                            "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
             if plan.antialias:
                 report[-1]["crop_minify"] = [round(plan.crop_minify[i], 6) for i in mine]
                 report[-1]["paste_minify"] = [round(plan.paste_minify[i], 6) for i in mine]
     writer.drain()
+    photo_writer.drain()
     name = "report.json" if world == 1 else "report_%d.json" % rank
     head = {"upscale": args.upscale, "crop_size": args.size, "inset": args.inset, "feather": args.feather}
     if restorer.color_fix is not None:
         head.update(color_fix=restorer.color_fix, color_levels=restorer.color_levels)
+    if jpg:
+        head.update(format="jpg", quality=args.quality, subsampling=args.subsampling)
     with open(os.path.join(args.out, name), "w") as f:
         json.dump(dict(head, photos=report), f, indent=1)
     return report
@@ -153,9 +166,21 @@ def main(argv=None):
                     help="before the paste the restored crop takes its colours back from the crop: per-channel mean and deviation (stats) "
                          "or everything below the finest --color_levels wavelet levels (wavelet)")
     ap.add_argument("--color_levels", type=int, default=5, help="levels of --color_fix wavelet, 1..6")
+    ap.add_argument("--format", choices=["png", "jpg"], default="png", help="file format of the output photos (the --save_faces files stay PNG)")
+    ap.add_argument("--quality", type=int, default=None, help="--format jpg: JPEG quality 1..100 (default 90)")
+    ap.add_argument("--subsampling", choices=["420", "444"], default=None, help="--format jpg: chroma subsampling (default 420)")
+    ap.add_argument("--encode", choices=["host", "device"], default=None,
+                    help="--format jpg: code the file on the device (default) or with Pillow on the host; equal bytes")
     args = ap.parse_args(argv)
     try:                       # the flags are checked before any model is loaded
         color_fix, color_levels = check_color_fix(args.color_fix, args.color_levels)
+        if args.format != "jpg" and (args.quality is not None or args.subsampling is not None or args.encode is not None):
+            raise ValueError("--quality, --subsampling and --encode belong to --format jpg")
+        if args.format == "jpg":
+            from .jpeg import DEFAULT_QUALITY, DEFAULT_RESTART, check_params
+            args.quality, args.subsampling, _ = check_params(DEFAULT_QUALITY if args.quality is None else args.quality,
+                                                              args.subsampling or "420", DEFAULT_RESTART)
+            args.encode = args.encode or "device"
     except ValueError as e:
         ap.error(str(e))
     if args.batch < 1 or args.inset < 0 or args.feather < 0:
