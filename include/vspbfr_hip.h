@@ -41,7 +41,7 @@ const char* vsp_last_error(void);
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
- * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item): lets a binding in
+ * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item, 12 = vsp_jpeg_dec_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -1016,6 +1016,73 @@ size_t vsp_jpeg_image_bound(int h, int w, int restart, int subsampling);
 int vsp_jpeg_encode_u8(uint8_t* out, size_t out_bytes, int32_t* totals, uint8_t* work, size_t work_bytes, int32_t* interval_ws,
                        const uint8_t* src, size_t src_bytes, const vsp_jpeg_item* items, const vsp_jpeg_item* items_dev, int n,
                        int quality, int subsampling, int restart, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device-side JPEG decoder: a ragged batch of baseline scans -> packed (h, w, 3) RGB uint8 images (csrc/jpeg_decode.hip).
+ * The host reads the markers in front of the scan (vspbfr_amd/jpeg.py parse) and hands over, per image, the entropy-coded bytes (from
+ * the byte behind the SOS header to the end of the file), the three quantisation tables and the six Huffman tables its components
+ * select.  Served: SOF0, 8 bits, Y Cb Cr, 4:4:4 or 4:2:0, one interleaved scan, any 8-bit quantisers, any Huffman tables, a restart
+ * interval or none.  tests/jpeg_dec_ref.py restates every step in NumPy; the pixels equal Pillow's Image.open(f).convert("RGB")
+ * (libjpeg's default decode: ISLOW inverse DCT, fancy h2v2 upsampling, jdcolor) byte for byte.
+ *
+ *   unstuff    the scan ends at the first marker other than RSTm; `00` behind a data `FF`, `FF` fill bytes and the RSTm markers are
+ *              dropped, every RSTm opens the next restart interval.  An image without a restart interval is one interval
+ *   entropy    an interval is cut into subsequences of `sub_bytes` clean bytes.  The decoder's state between two symbols is (block of
+ *              the MCU, zig-zag position).  Round 0 decodes every subsequence from its first bit in state (0, 0) until the bit position
+ *              reaches the subsequence's end and records the exit (bit position, state, blocks completed).  Round r + 1 decodes
+ *              subsequence i + 1 from the exit of i that round r recorded, if round r changed it.  The rounds end when one changed
+ *              nothing (at most: subsequences + 1); rounds[i] = the largest number of rounds, round 0 and the unchanged one included,
+ *              that an interval of image i took (1 for a single subsequence).  The true pass then stores the coefficients
+ *   symbols    the first length 1..16 at which the prefix is a code; none: one bit is consumed.  The symbol's low nibble s is the
+ *              number of value bits (consumed whatever s is).  DC: symbol > 11 is a bad category.  AC: s = 0 with run 15 skips 16
+ *              positions, any other s = 0 ends the block (a run with it is an error); otherwise k += run, and k > 63 ends the block
+ *              without a store.  Bits past the interval's end read as 1; in the interval's last subsequence fewer than 8 remaining bits,
+ *              all 1, in state (0, 0) are the padding.  Blocks past the interval's expected count are not stored
+ *   pixels     DC prediction per component within the interval, dequantisation, ISLOW inverse DCT + range limit; 4:2:0: fancy
+ *              upsampling over the ceil(w / 2) x ceil(h / 2) real chroma samples (the last real row / column repeats), plain 2 x 2
+ *              replication where ceil(w / 2) <= 2, as jdsample.c chooses; jdcolor
+ *   status[i]  0, or the OR of VSP_JPEG_DEC_*: the caller decodes such an image on the host.  Events of the speculative rounds do
+ *              not count, only those of the true pass
+ *   items      given twice: in host memory, checked before anything is launched, and the same table in device memory; so are the
+ *              tables: per image VSP_JPEG_DEC_TABLE_BYTES = 3 x 64 quantisers (uint8, natural order, component 0 1 2), then 6 x
+ *              (16 BITS + 256 HUFFVAL): DC and AC table of component 0, of 1, of 2.  interval0 = the intervals of the items before,
+ *              work_off = the sum of vsp_jpeg_decode_work_bytes of the items before
+ * VSP_EINVAL, nothing launched: a null pointer (rounds may be null), n outside 0 .. VSP_JPEG_MAX_ITEMS, sub_bytes not a multiple of 4 in
+ * 4..4096, h or w outside 1..65535, a subsampling other than VSP_JPEG_444 / VSP_JPEG_420, restart outside 0..65535, a scan of less than
+ * 1 or more than VSP_JPEG_DEC_MAX_SCAN_BYTES bytes, an item outside `in` or `out`, an out_off below the end of the item before (the images
+ * ascend in `out` and do not overlap), a wrong interval0 or work_off, a BITS array with more than 256 codes or one that fills or
+ * overfills the code space (the all-ones code must stay free: the 1-bit padding of an interval is told from a code by it), a `work` too small or not 16-byte aligned.  VSP_ENOTSUP: in, out or work of
+ * 2 GiB or more.  n = 0 returns VSP_OK.  vsp_jpeg_decode_work_bytes returns 0 for arguments outside the limits.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_JPEG_DEC_TABLE_BYTES 1824
+#define VSP_JPEG_DEC_MAX_SCAN_BYTES 0x0FFFFFFF   /* bit positions stay below 2^31 */
+#define VSP_JPEG_DEC_COEF_LIMIT 16383            /* twice what 8-bit samples can give a dequantised coefficient */
+#define VSP_JPEG_DEC_NO_EOI 1          /* the data ends without a marker */
+#define VSP_JPEG_DEC_STRAY_MARKER 2    /* the scan ends at a marker other than EOI */
+#define VSP_JPEG_DEC_RST_ORDER 4       /* an RSTm number that does not cycle 0..7 */
+#define VSP_JPEG_DEC_RST_COUNT 8       /* intervals other than ceil(MCUs / restart) */
+#define VSP_JPEG_DEC_BAD_CODE 16       /* a prefix that matches no code */
+#define VSP_JPEG_DEC_BAD_CATEGORY 32   /* a category above 11 (DC) or 10 (AC) */
+#define VSP_JPEG_DEC_RUN 64            /* a run that carries k past 63, or a run beside an end of block */
+#define VSP_JPEG_DEC_BLOCK_COUNT 128   /* an interval that does not end on its last block's last bit (+ padding) */
+#define VSP_JPEG_DEC_COEF_RANGE 256    /* a dequantised coefficient beyond VSP_JPEG_DEC_COEF_LIMIT */
+
+typedef struct vsp_jpeg_dec_item {
+  int64_t in_off;      /* byte offset of the entropy-coded data in `in` */
+  int64_t out_off;     /* byte offset of the (h, w, 3) image in `out`, rows of 3 w bytes without padding */
+  int64_t work_off;    /* byte offset of its work area in `work` */
+  int32_t in_len;      /* bytes of entropy-coded data (up to the end of the file: the kernel finds the EOI) */
+  int32_t h, w;
+  int32_t subsampling; /* VSP_JPEG_444 or VSP_JPEG_420 */
+  int32_t restart;     /* MCUs per restart interval, 0 = none */
+  int32_t interval0;   /* index of its first restart interval among all intervals of the call */
+} vsp_jpeg_dec_item;
+
+/* bytes of one image's work area (a multiple of 16) */
+size_t vsp_jpeg_decode_work_bytes(int h, int w, int in_len, int subsampling, int restart, int sub_bytes);
+int vsp_jpeg_decode_u8(uint8_t* out, size_t out_bytes, int32_t* status, int32_t* rounds, uint8_t* work, size_t work_bytes, const uint8_t* in,
+                       size_t in_bytes, const vsp_jpeg_dec_item* items, const vsp_jpeg_dec_item* items_dev, const uint8_t* tables,
+                       const uint8_t* tables_dev, int n, int sub_bytes, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -110,6 +110,11 @@ class JpegItem(C.Structure):
     _fields_ = [("src_off", C.c_int64), ("out_off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("interval0", C.c_int32), ("pad_", C.c_int32)]
 
 
+class JpegDecItem(C.Structure):
+    _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("work_off", C.c_int64)] + [
+        (n, C.c_int32) for n in ("in_len", "h", "w", "subsampling", "restart", "interval0")]
+
+
 DEGRADE_HAZE, DEGRADE_GREY = 1, 2            # vsp_degrade_item.flags (include/vspbfr_hip.h VSP_DEGRADE_*)
 DEGRADE_MAX_KSIZE, DEGRADE_MAX_SIZE, DEGRADE_MAX_ITEMS = 41, 2048, 1024
 WIN_UNIFORM7, WIN_GAUSS11 = 7, 11            # vsp_pair_stats_u8 window (include/vspbfr_hip.h VSP_WIN_*)
@@ -205,6 +210,7 @@ SIGNATURES = {
     "vsp_color_fix_u8": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p],
     "vsp_jpeg_intervals": [_i, _i, _i, _i],
     "vsp_jpeg_encode_u8": [_p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p],
+    "vsp_jpeg_decode_u8": [_p, C.c_size_t, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p, _i, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
@@ -213,7 +219,8 @@ _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C
           "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i], "vsp_lanczos_work_bytes": [_i, _i],
           "vsp_png_segment_bound": [_i, _i, _i], "vsp_png_bound": [_i, _i, _i],
           "vsp_niqe_work_bytes": [_i, _i, _i, _i],
-          "vsp_jpeg_interval_bound": [_i, _i], "vsp_jpeg_image_bound": [_i, _i, _i, _i]}
+          "vsp_jpeg_interval_bound": [_i, _i], "vsp_jpeg_image_bound": [_i, _i, _i, _i],
+          "vsp_jpeg_decode_work_bytes": [_i, _i, _i, _i, _i, _i]}
 
 
 def _load():
@@ -237,7 +244,7 @@ def _load():
     if lib.vsp_abi_version() != ABI_VERSION:
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
-                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem)):
+                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -40,6 +40,7 @@ int vsp_struct_size(int which) {
     case 9: return (int)sizeof(vsp_face_tile);
     case 10: return (int)sizeof(vsp_face_aa_item);
     case 11: return (int)sizeof(vsp_jpeg_item);
+    case 12: return (int)sizeof(vsp_jpeg_dec_item);
     default: return -1;
   }
 }

@@ -1,7 +1,8 @@
-// The JPEG compressor's integer arithmetic that the training degradation (degrade.hip: a round trip in the pixel domain) and the file
-// encoder (jpeg.hip) share: colour transform, 4:2:0 downsampling with the compressor's edge rule, ISLOW forward DCT, the
-// quality-scaled Annex K quantisation tables.  Bit-exact against libjpeg / libjpeg-turbo; tests/degrade_ref.py and tests/jpeg_ref.py
-// restate it in NumPy.
+// The JPEG codec's integer arithmetic that the training degradation (degrade.hip: a round trip in the pixel domain), the file encoder
+// (jpeg.hip) and the file decoder (jpeg_decode.hip) share.  Compressor: colour transform, 4:2:0 downsampling with the compressor's edge
+// rule, ISLOW forward DCT, the quality-scaled Annex K quantisation tables.  Decompressor: ISLOW inverse DCT with its range limit, fancy
+// h2v2 upsampling, YCbCr -> RGB.  Bit-exact against libjpeg / libjpeg-turbo; tests/degrade_ref.py, tests/jpeg_ref.py and
+// tests/jpeg_dec_ref.py restate it in NumPy.
 #pragma once
 #include "vsp_common.h"
 
@@ -108,6 +109,58 @@ __host__ __device__ inline void jpeg_chroma_h2v2(const JpegGeom& g, int cy, int 
   const int bias = (cx & 1) ? 2 : 1;
   cb = (sb + bias) >> 2;
   cr = (sr + bias) >> 2;
+}
+
+// ---- the decompressor's half (degrade.hip's round trip and the file decoder jpeg_decode.hip)
+// ISLOW inverse DCT of 8 values at stride `s` (jidctint.c).  Pass 1 (columns) leaves PASS1_BITS extra bits; pass 2 (rows) descales by
+// CONST_BITS + PASS1_BITS + 3 and applies the post-IDCT range limit: index (x & 1023) of a table that clamps x + 128 to [0, 255] for
+// |x| < 512 and wraps beyond, exactly as the library's table does.
+__host__ __device__ inline int idct_range_limit(int x) {
+  const int i = x & 1023;
+  return i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896;
+}
+
+template <bool kPass2>
+__host__ __device__ inline void idct8(int* d, int s) {
+  const int z2e = d[2 * s], z3e = d[6 * s];
+  const int z1 = (z2e + z3e) * F0541;
+  const int t2 = z1 - z3e * F1847, t3 = z1 + z2e * F0765;
+  const int t0 = (d[0] + d[4 * s]) * (1 << kConstBits), t1 = (d[0] - d[4 * s]) * (1 << kConstBits);
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  int o0 = d[7 * s], o1 = d[5 * s], o2 = d[3 * s], o3 = d[s];
+  const int z5 = (o0 + o1 + o2 + o3) * F1175;
+  const int y1 = -(o0 + o3) * F0899, y2 = -(o1 + o2) * F2562;
+  const int y3 = -(o0 + o2) * F1961 + z5, y4 = -(o1 + o3) * F0390 + z5;
+  o0 = o0 * F0298 + y1 + y3;
+  o1 = o1 * F2053 + y2 + y4;
+  o2 = o2 * F3072 + y2 + y3;
+  o3 = o3 * F1501 + y1 + y4;
+  const int sh = kPass2 ? kConstBits + kPass1Bits + 3 : kConstBits - kPass1Bits;
+  int r[8] = {descale(t10 + o3, sh), descale(t11 + o2, sh), descale(t12 + o1, sh), descale(t13 + o0, sh),
+              descale(t13 - o0, sh), descale(t12 - o1, sh), descale(t11 - o2, sh), descale(t10 - o3, sh)};
+  for (int i = 0; i < 8; ++i) d[i * s] = kPass2 ? idct_range_limit(r[i]) : r[i];
+}
+
+// jdcolor.c: R = Y + round(1.402 (Cr - 128)), B = Y + round(1.772 (Cb - 128)), G = Y + ((-0.34414 (Cb - 128) - 0.71414 (Cr - 128)) in
+// 16-bit fixed point, + ONE_HALF, arithmetic shift), each clamped to [0, 255]
+__host__ __device__ inline int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+__host__ __device__ inline void ycc_rgb(int y, int cb, int cr, int& r, int& g, int& b) {
+  cb -= 128, cr -= 128;
+  r = clamp255(y + ((91881 * cr + 32768) >> 16));
+  g = clamp255(y + ((-22554 * cb + 32768 - 46802 * cr) >> 16));
+  b = clamp255(y + ((116130 * cb + 32768) >> 16));
+}
+
+// h2v2 fancy upsampling (jdsample.c): each output takes 9/16, 3/16, 3/16, 1/16 of the four nearest chroma samples; column sums
+// 3 * nearer row + farther row, then (3 * this + neighbour + 8) >> 4 for even and + 7 for odd output columns.  Rows and columns past
+// the real chroma size repeat the last real one (jdmainct.c set_bottom_pointers, the first / last column cases).
+template <typename Cs>
+__host__ __device__ inline int fancy_h2v2(const JpegGeom& g, int y, int x, const Cs& cs) {
+  const int cy = y >> 1, cx = x >> 1;
+  const int cn = (y & 1) ? min(cy + 1, g.ch - 1) : max(cy - 1, 0);
+  const int nx = (x & 1) ? min(cx + 1, g.cw - 1) : max(cx - 1, 0);
+  const int this_sum = 3 * cs(cy, cx) + cs(cn, cx), next_sum = 3 * cs(cy, nx) + cs(cn, nx);
+  return (3 * this_sum + next_sum + ((x & 1) ? 7 : 8)) >> 4;
 }
 
 }  // namespace vsp_jpeg

@@ -1781,6 +1781,78 @@ def jpeg_encode(buffer, sizes, quality=90, subsampling="420", restart=8):
     return out, totals, [row[1] for row in rows]
 
 
+JPEG_DEC_TABLE_BYTES = 1824                  # include/vspbfr_hip.h VSP_JPEG_DEC_TABLE_BYTES: 3 x 64 quantisers + 6 x (16 BITS + 256 HUFFVAL)
+JPEG_DEC_SUB_BYTES = 256                     # default subsequence length, from the sweep of tools/bench_jpeg_decode.py
+JPEG_DEC_MAX_SCAN_BYTES = 0x0FFFFFFF
+
+
+def jpeg_decode_layout(specs, sub_bytes=JPEG_DEC_SUB_BYTES):
+    """What one vsp_jpeg_decode_u8 call over `specs` = [(in_off, in_len, h, w, subsampling number, restart), ...] needs: (rows, out_bytes,
+    work_bytes) -- per image the vsp_jpeg_dec_item fields with the images back to back in `out`.  None when the entry refuses a spec."""
+    rows, out, work, intervals = [], 0, 0, 0
+    for in_off, in_len, h, w, sub, restart in specs:
+        need = lib.vsp_jpeg_decode_work_bytes(h, w, in_len, sub, restart, sub_bytes)
+        if need == 0:
+            return None
+        rows.append((in_off, out, work, in_len, h, w, sub, restart, intervals))
+        m = 16 if sub == JPEG_SUBSAMPLING["420"] else 8
+        mcus = -(-h // m) * -(-w // m)
+        out, work, intervals = out + 3 * h * w, work + need, intervals + (-(-mcus // restart) if restart else 1)
+    return rows, out, work
+
+
+def jpeg_decode(comp, specs, tables, sub_bytes=None, out=None, out_offsets=None, want_rounds=False):
+    """Baseline JPEG scans -> packed RGB images on the current stream (vsp_jpeg_decode_u8, csrc/jpeg_decode.hip).  comp: 1-D uint8 device
+    tensor of entropy-coded bytes; specs: [(in_off, in_len, h, w, subsampling number, restart), ...]; tables: n x JPEG_DEC_TABLE_BYTES
+    uint8 on the host.  Returns (out uint8, status (n,) int32, rounds (n,) int32 or None, offsets): image i is out[offsets[i] :
+    offsets[i] + 3 h w] when status[i] == 0.  out / out_offsets: write into a caller's buffer at the caller's offsets.  Nothing is
+    synchronised: items and tables go up as one pinned block.  Wrong arguments raise RuntimeError (the entry's message); a call that
+    needs a buffer of 2 GiB or more raises NotImplementedError."""
+    import ctypes as Ct
+    import numpy as np
+    from ._lib import JpegDecItem
+    _u8(comp, "comp")
+    sub_bytes = JPEG_DEC_SUB_BYTES if sub_bytes is None else int(sub_bytes)
+    n, dev = len(specs), comp.device
+    tables = np.ascontiguousarray(tables, dtype=np.uint8).reshape(-1)
+    if comp.dim() != 1 or tables.size != n * JPEG_DEC_TABLE_BYTES:
+        raise RuntimeError(f"jpeg_decode: a flat buffer and {n} x {JPEG_DEC_TABLE_BYTES} table bytes, got {tuple(comp.shape)} and {tables.size}")
+    if sub_bytes < 4 or sub_bytes % 4:
+        raise RuntimeError(f"jpeg_decode: sub_bytes {sub_bytes} (a multiple of 4, at least 4)")
+    layout = jpeg_decode_layout(specs, sub_bytes)
+    if layout is None:
+        raise RuntimeError(f"jpeg_decode: specs {list(specs)}, sub_bytes {sub_bytes}")
+    rows, out_bytes, work_bytes = layout
+    if out is None:
+        out = torch.empty(out_bytes, device=dev, dtype=torch.uint8)
+    else:
+        _u8(out, "out")
+        rows = [(r[0], int(o)) + r[2:] for r, o in zip(rows, out_offsets)]
+        out_bytes = out.numel()
+    if n == 0:
+        return out, torch.empty(0, device=dev, dtype=torch.int32), torch.empty(0, device=dev, dtype=torch.int32) if want_rounds else None, []
+    if max(comp.numel(), out_bytes, work_bytes) >= JPEG_LIMIT_BYTES:
+        raise NotImplementedError(f"jpeg_decode: buffers of {comp.numel()}, {out_bytes} and {work_bytes} bytes reach the limit of "
+                                  "vsp_jpeg_decode_u8")
+    isz = Ct.sizeof(JpegDecItem)
+    block = torch.empty(n * (isz + JPEG_DEC_TABLE_BYTES), dtype=torch.uint8, pin_memory=True)
+    items = (JpegDecItem * n).from_address(block.data_ptr())
+    for i, row in enumerate(rows):
+        items[i] = JpegDecItem(*row)
+    block[n * isz:].copy_(torch.from_numpy(tables))
+    block_dev = block.to(dev, non_blocking=True)
+    work = torch.empty(work_bytes, device=dev, dtype=torch.uint8)
+    status = torch.empty(n, device=dev, dtype=torch.int32)
+    rounds = torch.empty(n, device=dev, dtype=torch.int32) if want_rounds else None
+    rc = lib.vsp_jpeg_decode_u8(_ptr(out), out_bytes, _ptr(status), _ptr(rounds) if want_rounds else None, _ptr(work), work_bytes, _ptr(comp),
+                                comp.numel(), Ct.c_void_p(block.data_ptr()), _ptr(block_dev), Ct.c_void_p(block.data_ptr() + n * isz),
+                                Ct.c_void_p(block_dev.data_ptr() + n * isz), n, sub_bytes, _stream())
+    if rc == -3:
+        raise NotImplementedError(_lib.last_error())
+    check(rc, "jpeg_decode")
+    return out, status, rounds, [row[1] for row in rows]
+
+
 # ----------------------------------------------------------------------------------------------- faces inside whole photos
 def _fwd_args(fwd_host, fwd):
     """the forward tables of a *_aa entry: host pointer, device pointer (both NULL when no face is filtered), entries; () for a plain entry"""

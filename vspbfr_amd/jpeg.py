@@ -9,7 +9,17 @@ Pillow's `save(format="JPEG", quality=, subsampling=, restart_marker_blocks=)` b
     assemble(segment, h, w, quality, subsampling, restart)           the host framing alone
 
 A call the kernel refuses for its size (a buffer of 2 GiB or more) is encoded by Pillow with the same parameters: the bytes a caller
-gets do not depend on the route."""
+gets do not depend on the route.
+
+The other direction (csrc/jpeg_decode.hip): the host reads the markers in front of the scan, the kernels decode the scan.
+The pixels equal Pillow's `Image.open(f).convert("RGB")` byte for byte (tests/jpeg_dec_ref.py restates every step).
+
+    parse(data) -> (Scan, None) | (None, reason)                     the markers in front of the scan; a reason = the host decodes
+    decode_batch(datas, device) -> (packed, sizes, offsets, how)     file contents -> (h, w, 3) images back to back on the device
+    decode_files(paths, device)                                      the same from paths
+
+A file the parser refuses (progressive, greyscale, 4:2:2, CMYK, ..., or no JPEG at all) and one whose scan the kernels flag (status word
+not 0) is decoded by Pillow and copied into its slot: results and exceptions are those of the host path, whatever the route."""
 import io
 
 import numpy as np
@@ -185,3 +195,194 @@ def encode_batch(u8, quality=DEFAULT_QUALITY, subsampling="420", restart=DEFAULT
         raise RuntimeError("jpeg.encode_batch: a contiguous (B, H, W, 3) uint8 tensor")
     B, H, W, _ = u8.shape
     return encode_ragged(u8.reshape(-1), [(H, W)] * B, quality, subsampling, restart)
+
+
+# ---------------------------------------------------------------------------------------------------------------------- decoder
+class Scan:
+    """what the kernels need of one baseline file: h, w, subsampling ('444' / '420'), restart (MCUs, 0 = none), qt (3, 64) uint8 in
+    natural order, huff [(BITS, HUFFVAL)] x 6 -- DC and AC table of component 0, of 1, of 2 -- and offset / length of the
+    entropy-coded data (to the end of the file: the kernel finds the EOI)"""
+    __slots__ = ("h", "w", "subsampling", "restart", "qt", "huff", "offset", "length")
+
+    def tables(self):
+        """VSP_JPEG_DEC_TABLE_BYTES: the quantisers, then 16 BITS + 256 HUFFVAL per table"""
+        out = np.zeros(3 * 64 + 6 * 272, dtype=np.uint8)
+        out[:192] = self.qt.reshape(-1)
+        for k, (bits, vals) in enumerate(self.huff):
+            at = 192 + k * 272
+            out[at:at + 16] = np.frombuffer(bits, dtype=np.uint8)
+            out[at + 16:at + 16 + len(vals)] = np.frombuffer(vals, dtype=np.uint8)
+        return out
+
+
+_SOF_REFUSED = {0xC1: "extended sequential (SOF1)", 0xC2: "progressive (SOF2)", 0xC3: "lossless (SOF3)", 0xCC: "arithmetic coding (DAC)"}
+_SOF_REFUSED.update({c: "hierarchical or arithmetic coding (SOF%d)" % (c - 0xC0) for c in (0xC5, 0xC6, 0xC7, 0xC9, 0xCA, 0xCB, 0xCD, 0xCE, 0xCF)})
+
+
+def _huff_refusal(bits, vals):
+    code = 0
+    for length in range(1, 17):
+        code += bits[length - 1]
+        if code > 1 << length:
+            return "a Huffman table overfills the code space"
+        if code == 1 << length:
+            return "a Huffman table uses the all-ones code"       # the padding of an interval could not be told from it
+        code <<= 1
+    if len(vals) != sum(bits) or sum(bits) > 256:
+        return "a Huffman table is cut short"
+    return None
+
+
+def parse(data):
+    """The markers in front of the scan of a JPEG file -> (Scan, None), or (None, reason) for a file the device path does not serve:
+    anything but SOF0 with 8 bits, components 1 2 3 sampled (1,1)(1,1)(1,1) or (2,2)(1,1)(1,1), 8-bit quantisers, one interleaved scan
+    and no Adobe APP14.  The entropy-coded data is never walked in Python: one vectorised search finds the marker that ends it."""
+    data = bytes(data)
+    if data[:2] != b"\xFF\xD8":
+        return None, "not a JPEG file (no SOI)"
+    qts, huff, pos, restart, frame, n = {}, {}, 2, 0, None, len(data)
+    while True:
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos + 3 > n or data[pos - 1] != 0xFF:
+            return None, "no SOS where a marker is expected"
+        code = data[pos]
+        pos += 1
+        if code == 0x01 or 0xD0 <= code <= 0xD7:
+            continue
+        size = int.from_bytes(data[pos:pos + 2], "big")
+        if code == 0xD9 or size < 2 or pos + size > n:
+            return None, "a segment runs past the end of the file"
+        seg = data[pos + 2:pos + size]
+        pos += size
+        if code in _SOF_REFUSED:
+            return None, _SOF_REFUSED[code]
+        if code == 0xEE and seg[:5] == b"Adobe":
+            return None, "Adobe APP14 (RGB, CMYK or YCCK coding)"
+        if code == 0xDC:
+            return None, "DNL"
+        if code == 0xDB:
+            for i in range(0, len(seg), 65):
+                if seg[i] >> 4:
+                    return None, "16-bit quantisation table"
+                if len(seg) - i < 65:
+                    return None, "a quantisation table is cut short"
+                qts[seg[i] & 15] = np.frombuffer(seg[i + 1:i + 65], dtype=np.uint8)
+        elif code == 0xC4:
+            i = 0
+            while i + 17 <= len(seg):
+                bits = seg[i + 1:i + 17]
+                huff[seg[i]] = (bits, seg[i + 17:i + 17 + sum(bits)])
+                i += 17 + sum(bits)
+        elif code == 0xC0:
+            frame = seg
+        elif code == 0xDD and len(seg) >= 2:
+            restart = int.from_bytes(seg[:2], "big")
+        elif code == 0xDA:
+            break
+    if frame is None or len(frame) < 6:
+        return None, "SOS before SOF"
+    if frame[0] != 8:
+        return None, f"{frame[0]}-bit samples"
+    h, w, nf = int.from_bytes(frame[1:3], "big"), int.from_bytes(frame[3:5], "big"), frame[5]
+    if h == 0 or w == 0:
+        return None, "a side of 0 (DNL)"
+    if nf != 3 or len(frame) != 15:
+        return None, "greyscale" if nf == 1 else f"{nf} components (CMYK / YCCK)"
+    comps = [(frame[6 + 3 * i], frame[7 + 3 * i] >> 4, frame[7 + 3 * i] & 15, frame[8 + 3 * i]) for i in range(3)]
+    if [c[0] for c in comps] != [1, 2, 3]:
+        return None, "component ids other than 1, 2, 3 (RGB-coded)"
+    sampling = [c[1:3] for c in comps]
+    if sampling not in ([(1, 1)] * 3, [(2, 2), (1, 1), (1, 1)]):
+        return None, "sampling factors %s (4:2:2, 4:4:0, ...)" % sampling
+    if len(seg) != 10 or seg[0] != 3:
+        return None, "a scan of %d components (several scans)" % (seg[0] if seg else 0)
+    if [seg[1], seg[3], seg[5]] != [1, 2, 3] or tuple(seg[7:10]) != (0, 63, 0):
+        return None, "a reordered or progressive scan"
+    s = Scan()
+    s.h, s.w, s.subsampling, s.restart, s.huff, qt = h, w, "420" if sampling[0] == (2, 2) else "444", restart, [], []
+    for i in range(3):
+        td, ta = seg[2 + 2 * i] >> 4, seg[2 + 2 * i] & 15
+        if td not in huff or (0x10 | ta) not in huff or comps[i][3] not in qts:
+            return None, "a table the scan selects is missing"
+        for t in (huff[td], huff[0x10 | ta]):
+            why = _huff_refusal(*t)
+            if why:
+                return None, why
+            s.huff.append(t)
+        nat = np.zeros(64, dtype=np.uint8)
+        nat[list(_ZIGZAG)] = qts[comps[i][3]]
+        qt.append(nat)
+    s.qt, s.offset, s.length = np.stack(qt), pos, n - pos
+    from .hip_ops import JPEG_DEC_MAX_SCAN_BYTES
+    if not 1 <= s.length <= JPEG_DEC_MAX_SCAN_BYTES:
+        return None, f"{s.length} bytes of entropy-coded data"
+    a = np.frombuffer(data, dtype=np.uint8, offset=pos)
+    nx = a[1:]
+    hit = np.flatnonzero((a[:-1] == 0xFF) & (nx != 0) & (nx != 0xFF) & ((nx & 0xF8) != 0xD0))
+    if hit.size and nx[hit[0]] != 0xD9:
+        return None, "marker %02X behind the scan (several scans, DNL)" % nx[hit[0]]
+    return s, None
+
+
+def host_pixels(data):
+    """the host route: Pillow's default decode of a file's contents"""
+    from PIL import Image
+    return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
+
+
+def decode_batch(datas, device, sub_bytes=None, want_rounds=False):
+    """File contents -> (packed uint8 device tensor of (h, w, 3) images back to back, [(h, w), ...], byte offsets, how) with how[i] in
+    {"device", "host"}; with want_rounds a fifth value, the kernel's round count per file (0 for a host file).  The compressed bytes
+    and one pinned block of items and tables go up on the current stream; the status words are read once, and a refused or flagged
+    file is decoded by Pillow -- whose exception, if it raises one, is the caller's -- and copied into its slot."""
+    from . import hip_ops
+    datas = [bytes(d) for d in datas]
+    scans = [parse(d)[0] for d in datas]
+    host = {i: host_pixels(d) for i, (d, s) in enumerate(zip(datas, scans)) if s is None}
+    sizes = [host[i].shape[:2] if s is None else (s.h, s.w) for i, s in enumerate(scans)]
+    offsets = [0] * len(datas)
+    for i in range(1, len(datas)):
+        offsets[i] = offsets[i - 1] + 3 * sizes[i - 1][0] * sizes[i - 1][1]
+    total = offsets[-1] + 3 * sizes[-1][0] * sizes[-1][1] if datas else 0
+    packed = torch.empty(total, device=device, dtype=torch.uint8)
+    rounds = [0] * len(datas)
+    dev = [i for i, s in enumerate(scans) if s is not None]
+    if dev and sum(scans[i].length for i in dev) >= hip_ops.JPEG_LIMIT_BYTES:
+        host.update({i: host_pixels(datas[i]) for i in dev})
+        dev = []
+    if dev:
+        comp = torch.empty(sum(scans[i].length for i in dev), dtype=torch.uint8, pin_memory=True)
+        view, specs, at = comp.numpy(), [], 0
+        for i in dev:
+            s = scans[i]
+            view[at:at + s.length] = np.frombuffer(datas[i], dtype=np.uint8, offset=s.offset)
+            specs.append((at, s.length, s.h, s.w, SUBSAMPLING[s.subsampling], s.restart))
+            at += s.length
+        tables = np.concatenate([scans[i].tables() for i in dev])
+        with torch.cuda.device(device):
+            try:
+                _, status, rnd, _ = hip_ops.jpeg_decode(comp.to(device, non_blocking=True), specs, tables, sub_bytes, out=packed,
+                                                        out_offsets=[offsets[i] for i in dev], want_rounds=want_rounds)
+                words = torch.stack([status, rnd]).cpu().numpy() if want_rounds else status.cpu().numpy()[None]
+            except NotImplementedError:
+                words = np.ones((1, len(dev)), dtype=np.int32)
+        for k, i in enumerate(dev):
+            if words[0, k]:
+                host[i] = host_pixels(datas[i])
+                assert host[i].shape[:2] == sizes[i]
+            elif want_rounds:
+                rounds[i] = int(words[1, k])
+    for i, arr in host.items():
+        packed[offsets[i]:offsets[i] + arr.size].copy_(torch.from_numpy(np.array(arr)).reshape(-1))
+    how = ["host" if i in host else "device" for i in range(len(datas))]
+    return (packed, sizes, offsets, how, rounds) if want_rounds else (packed, sizes, offsets, how)
+
+
+def decode_files(paths, device, sub_bytes=None):
+    """decode_batch over the contents of `paths` (a file that is no JPEG, a PNG for instance, takes the host decode in the same call)"""
+    datas = []
+    for p in paths:
+        with open(p, "rb") as f:
+            datas.append(f.read())
+    return decode_batch(datas, device, sub_bytes)

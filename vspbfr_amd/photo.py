@@ -192,6 +192,8 @@ def default_ramp(inset=DEFAULT_INSET, feather=DEFAULT_FEATHER):
 
 class FacePlan:
     """One ragged batch: `photos` (uint8 (h, w, 3) arrays) and `faces` = [(photo index, five landmarks), ...] in paste order.
+    device_photos: a flat uint8 device tensor that already holds the photos back to back (jpeg.decode_files); `photos` are then
+    their (h, w) -- pixels beside the tensor are refused --, upload() sends the tables alone and uses the tensor as its `photos` section.
 
     For face i: A_i = similarity_from_landmarks; the crop tables of M = A^-1 over the S x S crop; P = paste_matrix(A, upscale), its
     bounding box in the (upscale h, upscale w) output photo and the paste tables over that box.  The paste tiles: every 32 x 32 tile of
@@ -202,28 +204,43 @@ class FacePlan:
     keeps the four bilinear taps), the forward tables over the source range its filter windows touch and a vsp_face_aa_item; a
     minification above MAX_MINIFY is a ValueError.  Without it nothing of this is computed and pack() is unchanged."""
 
-    def __init__(self, photos, faces, size=512, upscale=1, names=None, antialias=False):
+    def __init__(self, photos, faces, size=512, upscale=1, names=None, antialias=False, device_photos=None):
         self.S, self.upscale, self.antialias = int(size), int(upscale), bool(antialias)
+        self.device_photos = device_photos
         if not 1 <= self.S <= MAX_SIDE or self.upscale < 1:
             raise ValueError(f"FacePlan: size {size}, upscale {upscale}")
         if len(faces) > MAX_ITEMS:
             raise ValueError(f"FacePlan: at most {MAX_ITEMS} faces")
         names = [str(k) for k in range(len(photos))] if names is None else list(names)
-        self.photos, self.src_off, self.out_off, self.out_shape = [], [], [], []
+        self.photos, self.shapes, self.src_off, self.out_off, self.out_shape = [], [], [], [], []
         src = out = 0
         for k, a in enumerate(photos):
-            a = np.asarray(a)
-            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
-                raise ValueError(f"photo {names[k]!r}: must be uint8 (h, w, 3), got {a.dtype} {a.shape}")
-            self.photos.append(np.ascontiguousarray(a))
+            if device_photos is not None:                  # the pixels are in device_photos: `a` is the photo's (h, w)
+                if hasattr(a, "dtype") or len(tuple(a)) != 2:
+                    raise ValueError(f"photo {names[k]!r}: with device_photos the photos are given as (h, w), not as pixels")
+                h, w = (int(v) for v in a)
+                if h < 1 or w < 1:
+                    raise ValueError(f"photo {names[k]!r}: shape {tuple(a)}")
+                self.photos.append(None)
+            else:
+                a = np.asarray(a)
+                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                    raise ValueError(f"photo {names[k]!r}: must be uint8 (h, w, 3), got {a.dtype} {a.shape}")
+                self.photos.append(np.ascontiguousarray(a))
+                h, w = a.shape[:2]
+            self.shapes.append((h, w))
             self.src_off.append(src)
             self.out_off.append(out)
-            self.out_shape.append((a.shape[0] * self.upscale, a.shape[1] * self.upscale))
-            src += a.size
-            out += a.size * self.upscale * self.upscale
+            self.out_shape.append((h * self.upscale, w * self.upscale))
+            src += 3 * h * w
+            out += 3 * h * w * self.upscale * self.upscale
         self.src_bytes, self.out_bytes = src, out
         if max(src, out) >= 1 << 31:
             raise ValueError("FacePlan: a batch of photos must stay below 2 GiB")
+        if device_photos is not None:
+            import torch
+            if device_photos.dtype != torch.uint8 or device_photos.dim() != 1 or device_photos.numel() != src or not device_photos.is_contiguous():
+                raise ValueError(f"FacePlan: device_photos must be a flat contiguous uint8 tensor of {src} bytes")
         S, n = self.S, len(faces)
         self.n = n
         self.face_photo, self.A, self.P, self.boxes = [], [], [], []
@@ -253,7 +270,7 @@ class FacePlan:
             if not 0 <= k < len(self.photos):
                 raise ValueError(f"face {i}: photo index {k}")
             j = which[k] = which.get(k, -1) + 1           # the face's number inside its photo, for messages
-            h, w = self.photos[k].shape[:2]
+            h, w = self.shapes[k]
             A = similarity_from_landmarks(pts, size=S, photo=names[k], face=j)
             P = paste_matrix(A, self.upscale)
             oh, ow = self.out_shape[k]
@@ -330,12 +347,14 @@ class FacePlan:
             for name, a in parts:
                 sections[name] = (off, a.size)
                 off = (off + a.size + 15) // 16 * 16
-            sections["photos"] = (off, self.src_bytes)
-            host = torch.empty(off + self.src_bytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+            held = self.device_photos is not None          # the photos are on the device already: the buffer ends behind the tables
+            if not held:
+                sections["photos"] = (off, self.src_bytes)
+            host = torch.empty(off + (0 if held else self.src_bytes), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
             hv = host.numpy()
             for name, a in parts:
                 hv[sections[name][0]:sections[name][0] + a.size] = a
-            for o, a in zip(self.src_off, self.photos):
+            for o, a in zip(self.src_off, () if held else self.photos):
                 hv[off + o:off + o + a.size] = a.reshape(-1)
             self._host = (host, sections)
         return self._host
@@ -348,6 +367,10 @@ class FacePlan:
             host, sections = self.pack()
             dev = host.to(device, non_blocking=True)
             self._dev = (device, {name: dev[o:o + nb] for name, (o, nb) in sections.items()})
+            if self.device_photos is not None:
+                if self.device_photos.device != dev.device:
+                    raise ValueError(f"FacePlan: device_photos is on {self.device_photos.device}, the plan goes to {dev.device}")
+                self._dev[1]["photos"] = self.device_photos
         return self._dev[1]
 
     def background(self, device):
@@ -360,7 +383,11 @@ class FacePlan:
             return dev["photos"].clone()
         from .resample import ResamplePlan, host_resize, kernel_serves
         out = torch.empty(self.out_bytes, dtype=torch.uint8, device=device)
-        for a, o, (oh, ow) in zip(self.photos, self.out_off, self.out_shape):
+        photos = self.photos
+        if self.device_photos is not None:                  # the resize takes its source from the host: one copy back for the group
+            back = self.device_photos.cpu().numpy()
+            photos = [back[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(self.src_off, self.shapes)]
+        for a, o, (oh, ow) in zip(photos, self.out_off, self.out_shape):
             h, w = a.shape[:2]
             if kernel_serves(w, h, ow, oh, (0, 0, ow, oh), (oh, ow)):
                 u8, _ = ResamplePlan([a], [(ow, oh)], [(0, 0)], (oh, ow)).run(device, u8=True, f32=False)
@@ -454,15 +481,16 @@ class PhotoRestorer:
         self.ramp = default_ramp(inset, feather)
         self.color_fix, self.color_levels = check_color_fix(color_fix, color_levels)
 
-    def __call__(self, photos, landmarks, device, names=None):
-        """photos: uint8 (h, w, 3) arrays; landmarks: per photo a list of (5, 2) point sets (None or [] for none) ->
+    def __call__(self, photos, landmarks, device, names=None, device_photos=None):
+        """photos: uint8 (h, w, 3) arrays -- or their (h, w) with device_photos, the packed device buffer that holds them back to back
+        (jpeg.decode_files) --; landmarks: per photo a list of (5, 2) point sets (None or [] for none) ->
         (output photos: device uint8 (upscale h, upscale w, 3) tensors, crops (F, S, S, 3) uint8, restored (F, S, S, 3) uint8, plan);
         with a colour fix a fifth element, the fixed crops (F, S, S, 3) uint8 that were pasted (`restored` stays the network's output)"""
         import torch
 
         from . import hip_ops
         faces = [(k, pts) for k, per in enumerate(landmarks) for pts in (per or [])]
-        plan = FacePlan(photos, faces, self.size, self.upscale, names, antialias=self.antialias)
+        plan = FacePlan(photos, faces, self.size, self.upscale, names, antialias=self.antialias, device_photos=device_photos)
         S = self.size
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)

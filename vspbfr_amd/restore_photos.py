@@ -2,7 +2,7 @@
 
     python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
         [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L]
-        [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] [--decode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
@@ -33,6 +33,11 @@ the default, or 444) with a restart interval of vspbfr_amd.jpeg.DEFAULT_RESTART 
 codes it on the device (vspbfr_amd.jpeg, csrc/jpeg.hip, DESIGN 18), --encode host hands the pixels to Pillow with the same parameters;
 both write the bytes Pillow writes for the pixels of the png route.  The --save_faces files stay PNG.  report.json then names the .jpg
 files and lists `format`, `quality` and `subsampling`.  Default png: nothing changes.
+
+--decode device: the group's files are read as bytes and baseline JPEGs are decoded on the device (vspbfr_amd.jpeg.decode_files,
+csrc/jpeg_decode.hip) into the buffer the crop kernel reads; a PNG, a progressive or otherwise refused JPEG and a file whose
+scan the kernels flag take Pillow's decode inside the same group.  Equal output bytes either way.  With the flag (host or device)
+report.json lists `decode` per photo.  Default: Pillow, nothing changes.
 
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
@@ -108,8 +113,14 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
     report = []
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
     for group in _groups(names[lo:hi], landmarks, args.batch):
-        photos = [_decode(os.path.join(args.photos, n)) for n in group]
-        outs, crops, restored, plan, *fixed = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
+        decode = getattr(args, "decode", None)
+        if decode == "device":
+            from .jpeg import decode_files
+            packed, sizes, _, how = decode_files([os.path.join(args.photos, n) for n in group], device)
+            outs, crops, restored, plan, *fixed = restorer(sizes, [landmarks.get(n) for n in group], device, names=group, device_photos=packed)
+        else:
+            photos, how = [_decode(os.path.join(args.photos, n)) for n in group], ["host"] * len(group)
+            outs, crops, restored, plan, *fixed = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
         for k, n in enumerate(group):
             stem = os.path.join(args.out, os.path.splitext(n)[0])
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
@@ -123,6 +134,8 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
                         writer.submit(fixed[0][i:i + 1], [f"{stem}_{j}_fixed.png"])
             report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ext, args.out),
                            "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
+            if decode is not None:
+                report[-1]["decode"] = how[k]
             if plan.antialias:
                 report[-1]["crop_minify"] = [round(plan.crop_minify[i], 6) for i in mine]
                 report[-1]["paste_minify"] = [round(plan.paste_minify[i], 6) for i in mine]
@@ -171,6 +184,8 @@ def main(argv=None):
     ap.add_argument("--subsampling", choices=["420", "444"], default=None, help="--format jpg: chroma subsampling (default 420)")
     ap.add_argument("--encode", choices=["host", "device"], default=None,
                     help="--format jpg: code the file on the device (default) or with Pillow on the host; equal bytes")
+    ap.add_argument("--decode", choices=["host", "device"], default=None,
+                    help="decode baseline JPEG inputs on the device or everything with Pillow on the host (the default); equal bytes")
     args = ap.parse_args(argv)
     try:                       # the flags are checked before any model is loaded
         color_fix, color_levels = check_color_fix(args.color_fix, args.color_levels)
