@@ -26,20 +26,12 @@
 // Epilogue, per 16-channel block: the sixteen position accumulators meet in LDS, one thread per (channel, tile) applies
 // A^T . A, the same fused operand chain as the direct kernel (demod, bias, two activations, noise, two residuals) and stores
 // the 2x2 pixels.  Numerics: F(2x2,3x3) in fp32 adds ~1e-6 relative error (transform constants are 1 and 1/2).
-#include "conv_kernel.h"
+#include "conv_wino2.h"
 #include <type_traits>
 
 namespace vspconv {
 
 namespace {
-
-// Wave-uniform operand through the scalar cache, whatever the compiler can prove about the index: the constant address space
-// makes the load an s_load (lgkmcnt).  As a per-lane global load it joins vmcnt and drags the latency of every prefetch in
-// flight into the interval (measured: 674 -> 802 us on 512 -> 512 at 64^2 when an unrelated edit flipped the compiler's choice).
-__device__ __forceinline__ float uload(const float* base, int idx) {
-  typedef const float __attribute__((address_space(4))) * cfp4;
-  return ((cfp4)(uintptr_t)base)[__builtin_amdgcn_readfirstlane(idx)];
-}
 
 // (round 3, tried: delaying the second half of the first generation of workgroups by 4-15 us so that the two resident workgroups of a
 //  CU run out of phase -- prologue / epilogue of one under the MFMA intervals of the other: no effect on 64 / 128 / 512 channels
@@ -52,16 +44,14 @@ constexpr int WCK = 4;      // input channels per chunk = one MFMA k-step
 constexpr int NTHR = 512;
 
 template <int MBW, int DMAX>
-struct WG {  // workgroup geometry: MBW 16-channel blocks x NBW 16-tile blocks (MBW * NBW = 8: 64 accumulator registers)
+struct WG : Wino2Tile<MBW> {  // workgroup geometry: MBW 16-channel blocks x NBW 16-tile blocks (MBW * NBW = 8: 64 accumulator registers)
+  using T = Wino2Tile<MBW>;
   // input channels per barrier interval: two MFMA k-steps where the LDS budget allows it (32-tile geometry: 61 KB, two
   // workgroups per CU) -- half the barriers and a transform task for every thread; one k-step otherwise
   static constexpr int IVC = MBW == 4 ? 8 : 4;
   static constexpr int KS = IVC / 4;
-  static constexpr int NBW = 8 / MBW;
-  static constexpr int WCO = 16 * MBW;
-  static constexpr int NTILE = 16 * NBW;
-  static constexpr int TLX = NBW == 8 ? 16 : 8;
-  static constexpr int TLY = NTILE / TLX;
+  static constexpr int TLX = T::NBW == 8 ? 16 : 8;
+  static constexpr int TLY = T::NTILE / TLX;
   static constexpr int PR = 2 * TLY + 2, PC = 2 * TLX + 2 * DMAX;  // PC: the widest patch row (dilation DMAX)
   // Patch ROW pitch (round 3, bank conflicts).  The transform reads a task's window as 16-byte rows (ds_read2_b64: 16-lane groups,
   // bank = dword mod 32); a group holds the 8 tile columns of TWO tile rows (window rows 2 apart), so with 8-tile-wide geometries
@@ -70,16 +60,11 @@ struct WG {  // workgroup geometry: MBW 16-channel blocks x NBW 16-tile blocks (
   // from one row and keep the dense image; so do the dilated variants (their row width depends on the group's dilation).
   static constexpr int PCP = (DMAX == 1 && TLX == 8) ? 24 : PC;
   static constexpr int PPITCH = (PR * PCP + 15) / 16 * 16;
-  static constexpr int VPITCH = NTILE + 16;           // k-slot rows 16 banks apart
+  static constexpr int VPITCH = T::NTILE + 16;           // k-slot rows 16 banks apart
   static constexpr int LDS_V = 16 * IVC * VPITCH;     // floats, two buffers
   static constexpr int LDS_P = IVC * PPITCH;          // floats, two buffers
-  static constexpr int ETILE = NTILE > 64 ? 64 : NTILE;  // tiles per epilogue pass
-  static constexpr int EMB = (MBW >= 2 && ETILE <= 32) ? 2 : 1;  // 16-channel blocks per epilogue pass
-  static constexpr int EP = ETILE + 4;                // epilogue row pitch: 4 rows (one k-slot group) = 16 banks
-  static constexpr int LDS_M = 16 * 16 * EMB * EP;
   static constexpr int LDS_STAGE = 2 * LDS_V + 2 * LDS_P;
-  static constexpr int LDS_FLOATS = LDS_STAGE > LDS_M ? LDS_STAGE : LDS_M;
-  static constexpr int UF = 2 * MBW;                  // U floats per lane and chunk: [pp 2][mb MBW]
+  static constexpr int LDS_FLOATS = LDS_STAGE > T::LDS_M ? LDS_STAGE : T::LDS_M;
 };
 
 template <int MBW, int DMAX>
@@ -97,75 +82,20 @@ __global__ __launch_bounds__(NTHR, 4) void conv_wino_kernel(const ConvK p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, kq = lane >> 4;
-  // XCD-aware work order.  The dispatcher deals workgroups round-robin over the 8 XCDs (each with its own 4 MB L2), so in
-  // dispatch order every L2 sees every pixel tile and every channel tile.  Bijective remap: XCD x walks a CONTIGUOUS range of
-  // the work list, ordered either
-  //   1 = pixel-tile-major (image, pixel tile, channel tile): neighbouring tiles share their halo (40 % of a 10 x 18 patch)
-  //       and the channel tiles of one pixel tile read the same patch -- right when U is small (<= 64 channels), or
-  //   2 = channel-tile-major (channel tile, image, pixel tile): a workgroup streams its whole U slice (64 co x Cin x 16
-  //       positions x 4 B = 2 MB at 512 channels) and NO two waves share any of it, so U is the kernel's dominant fetch
-  //       (32 KB per 8-channel interval against 5.8 KB of patch: 4.3 GB per 512 -> 512 launch at 64^2, ~5 TB/s).  In
-  //       pixel-major order all 8 channel tiles (16.8 MB) compete for one 4 MB L2 and U streams from MALL / HBM; in
-  //       channel-major order an XCD works on one or two channel tiles at a time and U stays L2-resident.
-  //   4 = region-major (shared-input dilation groups, as in conv_bf16.hip): a region = one image band of 8 x 2 TLY rows x 4 column
-  //       tiles; for every dilation d | 8 exactly 8 workgroups per column tile cover it (d residues x 8/d row tiles), and the four
-  //       groups of a region run back to back on one XCD instead of never meeting in an L2.
+  // XCD-aware work order (conv_wino2.h): region-major (4), pixel-tile-major (1), channel-tile-major (2) or dispatch order
   int b = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
   int reg_ry = -1, reg_ty = 0, reg_tx = 0;
   if (DMAX > 1 && p.wg_order == 4) {
-    constexpr int CGX = 4;
-    const int GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z, GT = GX * GY * GZ;
-    const int wgid = blockIdx.x + GX * (blockIdx.y + GY * blockIdx.z);
-    const int xcd = wgid & 7, xq = GT >> 3, xr = GT & 7;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wgid >> 3);
-    const int nb = p.tiles_y, ncg = p.tiles_x;                 // (host: bands per image, column groups per band)
-    const int per_region = GY * 8 * CGX;
-    const int region = lid / per_region, w = lid - region * per_region;
-    b = region / (nb * ncg);
-    const int rr = region - b * (nb * ncg);
-    const int band = rr / ncg, cg = rr - band * ncg;
-    const int slot = w / (GY * CGX), w2 = w - slot * (GY * CGX);
-    const int cx = w2 / GY;
-    by = w2 - cx * GY;
-    const int dg = p.dil[by / p.co_tiles];
-    reg_ry = slot % dg;
-    reg_ty = band * (8 / dg) + slot / dg;
-    reg_tx = cg * CGX + cx;
+    decode_region_major(p, xcd_linear_id(), b, by, reg_ry, reg_ty, reg_tx);
   } else if (p.wg_order) {
-    const int GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z, GT = GX * GY * GZ;
-    const int wgid = blockIdx.x + GX * (blockIdx.y + GY * blockIdx.z);
-    const int xcd = wgid & 7, xq = GT >> 3, xr = GT & 7;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wgid >> 3);
-    if (p.wg_order == 1) {
-      const int GN = GX * GY;
-      b = lid / GN;
-      const int lrem = lid - b * GN;
-      bx = lrem / GY;
-      by = lrem - bx * GY;
-    } else {
-      const int GN = GX * GZ;
-      by = lid / GN;
-      const int lrem = lid - by * GN;
-      b = lrem / GX;
-      bx = lrem - b * GX;
-    }
+    const int lid = xcd_linear_id();
+    if (p.wg_order == 1) decode_pixel_major(lid, b, bx, by);
+    else decode_channel_major(lid, b, bx, by);
   }
   const int g = by / p.co_tiles, ct = by - g * p.co_tiles;
   const int d = DMAX == 1 ? 1 : p.dil[g];                     // row-polyphase stride and column tap spacing (1, 2, 4 or 8)
-  const int SH = (p.H + d - 1) / d;                           // rows of one residue class
-  const int tiles_x = (p.W + 2 * TLX - 1) / (2 * TLX), tiles_y = (SH + 2 * TLY - 1) / (2 * TLY);
-  const int per_res = tiles_x * tiles_y;
   int ry, tx_i, ty_i;
-  if (reg_ry >= 0) {
-    if (reg_ty >= tiles_y || reg_tx >= tiles_x) return;       // (bands / column groups that the image does not fill)
-    ry = reg_ry; ty_i = reg_ty; tx_i = reg_tx;
-  } else {
-    if (bx >= per_res * d) return;                            // (row counts that d does not divide leave a few spare blocks)
-    ry = bx / per_res;
-    const int tile_i = bx - ry * per_res;
-    tx_i = tile_i % tiles_x;
-    ty_i = tile_i / tiles_x;
-  }
+  if (!wino2_tile<TLX, TLY>(p, d, bx, reg_ry, reg_ty, reg_tx, ry, ty_i, tx_i)) return;
   const int oy0 = ty_i * (2 * TLY), ox0 = tx_i * (2 * TLX);   // sub-image rows, image columns
   const int PC = 2 * TLX + 2 * d;                             // patch row of this group
   const int PCP = PADROW ? Gm::PCP : PC;                      // its pitch in LDS
@@ -423,109 +353,8 @@ __global__ __launch_bounds__(NTHR, 4) void conv_wino_kernel(const ConvK p) {
   if (ab & 0x8000) return;
 #endif
 
-  // ---- epilogue: per 16-channel block and (at most) 64 tiles, all sixteen positions through LDS, one thread per
-  //      (channel, tile): Y = A^T M A, then the fused operand chain of the direct kernel
-  constexpr int ETILE = Gm::ETILE, ENB = ETILE / 16, EP = Gm::EP;
-  float* Ml = smem;  // [16 pos][16 co][EP]: rows padded so that the four k-slot groups of a store land 16 banks apart
-  const int Cout = p.G * p.cout_g;
-  const float* osp = p.osp + (int64_t)b * Cout * p.oss;
-  const float* nzp = p.nzp + (int64_t)b * p.OH * p.OW * p.nzs;
-  const float nw = p.nwp[0];
-  float* yb = p.y + ((int64_t)b * p.y_ch + p.y_coff) * p.y_h * p.y_w;
-  const float* r1b = p.r1p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r1s;
-  const float* r2b = p.r2p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r2s;
-  const int y_plane = p.y_h * p.y_w;
-  constexpr int EMB = Gm::EMB, ECO = 16 * EMB;
-  constexpr int EPT = ECO * ETILE / NTHR;  // (channel, tile) pairs per thread and pass
-  typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-  const bool vec2 = d == 1 && p.r1s <= 1 && p.r2s <= 1;  // the two pixels of a tile row are neighbours in memory
-  const bool pairs = vec2 && (p.OW & 1) == 0 && p.OW >= 2;
-#pragma unroll
-  for (int mb0 = 0; mb0 < MBW; mb0 += EMB) {
-#pragma unroll
-    for (int th = 0; th < NTILE / ETILE; ++th) {  // tile halves (only the 128-tile geometry has two)
-      if (mb0 + th > 0) __syncthreads();           // (the chunk loop ended on a barrier)
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-        for (int m2 = 0; m2 < EMB; ++m2)
-#pragma unroll
-          for (int nb = 0; nb < ENB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              Ml[((2 * wave + pp) * ECO + m2 * 16 + kq * 4 + r) * EP + nb * 16 + lr] = acc[pp][mb0 + m2][th * ENB + nb][r];
-      __syncthreads();
-#pragma unroll
-      for (int it = 0; it < EPT; ++it) {
-        const int pair = tid + it * NTHR;
-        const int e_co = pair / ETILE, e_t = pair - e_co * ETILE;
-        const int e_tile = th * ETILE + e_t;
-        const int e_tx = e_tile % TLX;
-        const int sy = oy0 + 2 * (e_tile / TLX);
-        const int sx = ox0 + (DMAX == 1 ? 2 * e_tx : (e_tx % d) + 2 * d * (e_tx / d));   // first output column of the tile
-        float m[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) m[q] = Ml[(q * ECO + e_co) * EP + e_t];
-        float t0[4], t1[4];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-          t0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
-          t1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
-        }
-        const float yv[2][2] = {{t0[0] + t0[1] + t0[2], t0[1] - t0[2] - t0[3]}, {t1[0] + t1[1] + t1[2], t1[1] - t1[2] - t1[3]}};
-        // No load sits behind a divergent branch (a ragged channel tile, an edge tile): coordinates are clamped, only the STORE is
-        // predicated.  With `continue` / edge tests in front of them the compiler waited for every load in flight at each join --
-        // the six per-channel operands and the noise / residual pairs of a thread left one round trip after the other.
-        const int cgi = co0 + mb0 * 16 + e_co;  // channel within the group
-        const bool cok = cgi < p.cout_g;
-        const int cg = g * p.cout_g + (cok ? cgi : p.cout_g - 1);
-        const float os = osp[cg * p.oss], cs = p.csp[cg * p.css], cb = p.cbp[cg * p.cbs];
-        const float b1 = p.b1p[cg * p.b1s], b2 = p.b2p[cg * p.b2s], sl2 = p.s2p[cg * p.s2s];
-        const int cbase = cg * y_plane;
-        auto fin = [&](float v, float nz, float r1v, float r2v) {
-          v = v * os * cs + cb + b1;
-          v = (v > 0.f ? v : v * p.s1) * p.g1;
-          v += nz * nw + b2;
-          v = (v > 0.f ? v : v * sl2) * p.g2;
-          return v + r1v + r2v;
-        };
-        if (pairs) {   // (uniform) even output width: a tile's two pixels are a whole 8-byte pair or lie outside together
-          f32x2u nz[2] = {{0.f, 0.f}, {0.f, 0.f}}, r1v[2] = {{0.f, 0.f}, {0.f, 0.f}}, r2v[2] = {{0.f, 0.f}, {0.f, 0.f}};
-          int ro[2];
-          bool inside[2];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = (sy + i) * d + ry;
-            inside[i] = cok && oy < p.OH && sx < p.OW;
-            const int oyc = min(oy, p.OH - 1), oxc = min(sx, p.OW - 2);
-            ro[i] = cbase + oyc * p.y_w + oxc;
-            if (p.nzs) nz[i] = *reinterpret_cast<const f32x2u*>(nzp + oyc * p.OW + oxc);
-            if (p.r1s) r1v[i] = *reinterpret_cast<const f32x2u*>(r1b + ro[i]);
-            if (p.r2s) r2v[i] = *reinterpret_cast<const f32x2u*>(r2b + ro[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const f32x2u o2 = {fin(yv[i][0], nz[i][0], r1v[i][0], r2v[i][0]), fin(yv[i][1], nz[i][1], r1v[i][1], r2v[i][1])};
-            if (inside[i]) *reinterpret_cast<f32x2u*>(yb + ro[i]) = o2;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = (sy + i) * d + ry, ox = sx;
-            if (!cok || oy >= p.OH || ox >= p.OW) continue;
-            const int ro = cbase + oy * p.y_w + ox;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              const int oxj = ox + j * d;
-              if (oxj >= p.OW) continue;
-              const int rj = ro + j * d;
-              yb[rj] = fin(yv[i][j], nzp[(oy * p.OW + oxj) * p.nzs], r1b[rj * p.r1s], r2b[rj * p.r2s]);
-            }
-          }
-        }
-      }
-    }
-  }
+  // ---- epilogue (conv_wino2.h)
+  wino2_epilogue<NTHR, MBW, NBW, TLX, Gm::ETILE, Gm::EMB, Gm::EP>(p, smem, acc, b, g, co0, oy0, ox0, d, ry, tid, wave, lr, kq);
 }
 
 template <int MBW, int DMAX>
@@ -535,14 +364,8 @@ int launch_variant(ConvK q, hipStream_t stream) {
   const size_t lds = (size_t)Gm::LDS_FLOATS * sizeof(float);
   if (int rc = attr.ensure(reinterpret_cast<const void*>(conv_wino_kernel<MBW, DMAX>), (int)lds, "conv2d_winograd")) return rc;
   q.co_tiles = (q.cout_g + Gm::WCO - 1) / Gm::WCO;
-  int blocks = 0;  // the largest per-group tile count (groups with a smaller dilation exit early)
-  for (int g = 0; g < q.G; ++g) {
-    const int d = q.dil[g];
-    const int SH = (q.H + d - 1) / d;
-    const int n = ((q.W + 2 * Gm::TLX - 1) / (2 * Gm::TLX)) * ((SH + 2 * Gm::TLY - 1) / (2 * Gm::TLY)) * d;
-    blocks = n > blocks ? n : blocks;
-  }
-  // work order (see the kernel): channel-tile-major once the launch's U no longer fits an L2 beside the patches
+  int blocks = wino2_group_blocks(q, Gm::TLX, Gm::TLY);
+  // work order (conv_wino2.h): channel-tile-major once the launch's U no longer fits an L2 beside the patches
   const int64_t u_bytes = (int64_t)q.G * q.co_tiles * Gm::WCO * ((q.Cin + 3) / 4 * 4) * 16 * 4;
   (void)u_bytes;  // measured: the order makes no difference on the big-U layers (512 -> 512 at 64^2: 772 us either way), pixel-major
                   // wins on 32 -> 32 at 1024^2 (1613 -> 1502 us) and on the dilation groups of small maps (512 -> 4 x 128 at 32^2: 437 -> 341 us)
@@ -552,12 +375,7 @@ int launch_variant(ConvK q, hipStream_t stream) {
   if (DMAX > 1 && q.G >= 2 && q.x_gs == 0 && !(q.dbg & 0x800000)) {
     bool ok = true;
     for (int g = 0; g < q.G; ++g) ok = ok && (q.dil[g] == 1 || q.dil[g] == 2 || q.dil[g] == 4 || q.dil[g] == 8);
-    if (ok) {  // region-major order over bands of 8 x 2 TLY rows x 4 column tiles
-      q.wg_order = 4;
-      q.tiles_y = (q.H + 16 * Gm::TLY - 1) / (16 * Gm::TLY);
-      q.tiles_x = ((q.W + 2 * Gm::TLX - 1) / (2 * Gm::TLX) + 3) / 4;
-      blocks = q.tiles_y * q.tiles_x * 32;
-    }
+    if (ok) wino2_region_major(q, Gm::TLY, Gm::TLX, &blocks);
   }
   dim3 grid((unsigned)blocks, (unsigned)(q.co_tiles * q.G), (unsigned)q.B);
   conv_wino_kernel<MBW, DMAX><<<grid, NTHR, lds, stream>>>(q);

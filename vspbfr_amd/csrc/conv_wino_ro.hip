@@ -15,31 +15,24 @@
 // The style scale / folded-BatchNorm affine are applied when the patch is committed (they are per input channel), so the fragment
 // path carries no multiply.  U (fragment order, conv_wino.hip / weight_pack.hip), tile geometry, work order and the epilogue are
 // those of conv_wino.hip: the two kernels are interchangeable per launch (wino_launch picks).
-#include "conv_kernel.h"
+#include "conv_wino2.h"
 #include <type_traits>
 
 namespace vspconv {
 
 namespace {
 
-__device__ __forceinline__ float uload_ro(const float* base, int idx) {  // wave-uniform operand through the scalar cache
-  typedef const float __attribute__((address_space(4))) * cfp4;
-  return ((cfp4)(uintptr_t)base)[__builtin_amdgcn_readfirstlane(idx)];
-}
-
 constexpr int RO_NTHR = 512;
 
-constexpr int IVC = 8;   // input channels per sub-stage: one channel plane per wave
+constexpr int IVC = WINO2_RO_IVC;   // input channels per sub-stage: one channel plane per wave
 
 template <int MBW, int TLX_ = 8>
-struct RG {  // geometry (undilated): MBW 16-channel blocks x NBW 16-tile blocks per wave and position, MBW * NBW = 8; TLX_ tile columns
+struct RG : Wino2Tile<MBW> {  // geometry (undilated): MBW 16-channel blocks x NBW 16-tile blocks per wave and position, MBW * NBW = 8; TLX_ tile columns
              // per workgroup (8: 16 x 16 pixels at 32 tiles; 16: 32 x 8 pixels -- 128-byte output row segments)
+  using T = Wino2Tile<MBW>;
   static constexpr int KS = IVC / 4;
-  static constexpr int NBW = 8 / MBW;
-  static constexpr int WCO = 16 * MBW;
-  static constexpr int NTILE = 16 * NBW;
-  static constexpr int TLX = NBW == 8 ? 16 : TLX_;
-  static constexpr int TLY = NTILE / TLX;
+  static constexpr int TLX = T::NBW == 8 ? 16 : TLX_;
+  static constexpr int TLY = T::NTILE / TLX;
   static constexpr int PR = 2 * TLY + 2;
   // Patch rows are staged as ALIGNED 16-byte segments: image columns ox0 - 4 ... ox0 + 2 TLX + 3 (W % 4 == 0: a segment lies inside the
   // image or outside as a whole, so validity is one bit per lane and the load is one buffer_load_dwordx4), SEG segments per row.
@@ -53,12 +46,7 @@ struct RG {  // geometry (undilated): MBW 16-channel blocks x NBW 16-tile blocks
   static constexpr int PPITCH = (PR * PCP + 1 + 31) / 64 * 64 + 32;
   static constexpr int NLD = (PR * SEG + 63) / 64;    // wave loads per channel plane (one for the 8-tile-wide geometries: 10 x 6 segments)
   static constexpr int LDS_P = IVC * PPITCH;          // floats per sub-stage buffer (ring of 2 M)
-  static constexpr int ETILE = NTILE > 64 ? 64 : NTILE;
-  static constexpr int EMB = (MBW >= 2 && ETILE <= 32) ? 2 : 1;
-  static constexpr int EP = ETILE + 4;
-  static constexpr int LDS_M = 16 * 16 * EMB * EP;
-  static constexpr int lds_floats(int m) { return 2 * m * LDS_P > LDS_M ? 2 * m * LDS_P : LDS_M; }
-  static constexpr int UF = 2 * MBW;
+  static constexpr int lds_floats(int m) { return 2 * m * LDS_P > T::LDS_M ? 2 * m * LDS_P : T::LDS_M; }
 };
 
 // M = barrier period in sub-stages of 8 input channels.  The patch lives in a ring of R = 2 M sub-stage buffers; sub-stage s reads
@@ -78,19 +66,9 @@ __global__ __launch_bounds__(RO_NTHR, 4) void conv_wino_ro_kernel(const ConvK p)
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, kq = lane >> 4;
-  // work order: pixel-tile-major per XCD (conv_wino.hip, order 1) or dispatch order
+  // work order: pixel-tile-major per XCD (conv_wino2.h, order 1) or dispatch order
   int b = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
-  if (p.wg_order) {
-    const int GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z, GT = GX * GY * GZ;
-    const int wgid = blockIdx.x + GX * (blockIdx.y + GY * blockIdx.z);
-    const int xcd = wgid & 7, xq = GT >> 3, xr = GT & 7;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wgid >> 3);
-    const int GN = GX * GY;
-    b = lid / GN;
-    const int lrem = lid - b * GN;
-    bx = lrem / GY;
-    by = lrem - bx * GY;
-  }
+  if (p.wg_order) decode_pixel_major(xcd_linear_id(), b, bx, by);
   const int g = by / p.co_tiles, ct = by - g * p.co_tiles;
   const int tiles_x = (p.W + 2 * TLX - 1) / (2 * TLX);
   const int tx_i = bx % tiles_x, ty_i = bx / tiles_x;
@@ -122,66 +100,22 @@ __global__ __launch_bounds__(RO_NTHR, 4) void conv_wino_ro_kernel(const ConvK p)
     p_dst[i] = 1 + r * PCP + 4 * sg;
   }
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.x_ch * chw * 4, 0x00020000);   // this image (the range check compares the lane offset with size - scalar offset)
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   f32x4v preg[NLD];
-  auto load_plane = [&](int j, f32x4v (&dst)[NLD]) {    // this wave's plane of sub-stage j (clamped: past the end the last one is loaded again)
-    const int jj = j < nstage ? j : nstage - 1;
-    const int ci = jj * IVC + wave;
-    const bool chin = ci < p.Cin;                                  // (a channel past the layer: every lane offset out of range -> zeros)
-    const int soff = (chin ? ci : 0) * chw * 4;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) dst[i] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, chin ? p_voff[i] : 0x7ffffff0, soff, 0));
-  };
-  const float* wt_b = p.wtp + b * p.wt_bs;   // (per-image bases hoisted: the interval's scalar address arithmetic is part of its issue time)
+  auto load_plane = [&](int j, f32x4v (&dst)[NLD]) { wino2_load_plane<NLD>(xrsrc, p_voff, j, nstage, wave, p.Cin, chw, dst); };
+  const float* wt_b = p.wtp + b * p.wt_bs;
   const float* wc_b = p.wcp + b * p.wc_bs;
   const bool affine = p.wc_cs != 0 || p.wsh_cs != 0 || p.wc_bs != 0;
-  auto commit_plane = [&](float* Pdst, int j, const f32x4v (&src)[NLD]) {   // style scale and (folded BatchNorm) affine ride on the patch
-    const int ci = j * IVC + wave;
-    const bool chok = ci < p.Cin;
-    const int cc = chok ? ci : p.Cin - 1;
-    const float st = uload_ro(wt_b, cc * p.wt_cs);
-    float sc = st, sh = 0.f;
-    if (affine) {   // (uniform for the launch) folded-BatchNorm input of the IR-SE body; the modulated layers skip two scalar loads and their address arithmetic
-      sc = uload_ro(wc_b, cc * p.wc_cs) * st;
-      sh = uload_ro(p.wshp, cc * p.wsh_cs) * st;
-    }
-    float* dst = Pdst + wave * PPITCH;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      // (These 16-byte writes start at word 1 + 4 l: NOT 16-byte aligned, served as four dword passes with the lanes four banks apart --
-      //  14 conflict cycles per write, 27 % of the kernel's LDS-active cycles (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.27; with the
-      //  commits switched off 0.008).  Writing the ALIGNED unit (d of segment l - 1 through DPP wave_shr:1, a, b, c) takes the ratio to
-      //  0.015 and the kernel from 605 to 630 us at 256 -> 256 / 128^2, 1211 to 1378 us at 32 -> 32 / 1024^2: the LDS is not what this
-      //  kernel waits for, the extra VALU on the commit path is.  Kept misaligned.)
-      // padding and absent channels arrive as ZEROS (out-of-range lane offset): only the affine shift still has to be masked, one select
-      // per segment -- no zero FACTOR that would turn an Inf / NaN at a clamped address into a NaN border
-      const float shm = (((p_ok >> i) & 1u) && chok) ? sh : 0.f;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[p_dst[i] + e] = fmaf(src[i][e], sc, shm);
-    }
+  auto commit_plane = [&](float* Pdst, int j, const f32x4v (&src)[NLD]) {
+    wino2_commit_plane<NLD>(p, wt_b, wc_b, affine, Pdst, PPITCH, j, wave, p_ok, p_dst, src);
   };
 
-  // ---- U fragments: [group][co tile][chunk][wave][pp 2][lane][mb MBW] floats, one 4-channel chunk (k-step) and position per load.
-  //      Buffer loads: resource = this channel tile's slice, scalar offset = chunk, lane offset fixed (a flat pointer costs a 64-bit VALU
-  //      add per load and a handful of scalar instructions for the 64-bit chunk offset: 56 SALU + 60 VALU per 32 MFMAs were measured).
+  // ---- U fragments (wino2_load_u_half): resource = this channel tile's slice
   const float* utile = p.w + ((int64_t)g * p.co_tiles + ct) * nchunk4 * (8 * 64 * UF);
   const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(utile), 0, nchunk4 * (8 * 64 * UF) * 4, 0x00020000);
   const int u_voff = ((wave * 2 * 64 + lane) * MBW) * 4;
   auto load_u_half = [&](int c, int pp, float (&u)[UF]) {
     if (ab & 4) return;
-    const int cc = (ab & 64) ? 0 : (c < nchunk4 ? c : nchunk4 - 1);
-    const int soff = cc * (8 * 64 * UF * 4);
-    if constexpr (MBW == 4) {
-      typedef float f32x4b __attribute__((ext_vector_type(4)));
-      const f32x4b a = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(ursrc, u_voff + pp * 64 * MBW * 4, soff, 0));
-      u[pp * 4 + 0] = a[0]; u[pp * 4 + 1] = a[1]; u[pp * 4 + 2] = a[2]; u[pp * 4 + 3] = a[3];
-    } else if constexpr (MBW == 2) {
-      typedef float f32x2b __attribute__((ext_vector_type(2)));
-      const f32x2b a = __builtin_bit_cast(f32x2b, __builtin_amdgcn_raw_buffer_load_b64(ursrc, u_voff + pp * 64 * MBW * 4, soff, 0));
-      u[pp * 2 + 0] = a[0]; u[pp * 2 + 1] = a[1];
-    } else {
-      u[pp] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ursrc, u_voff + pp * 64 * MBW * 4, soff, 0));
-    }
+    wino2_load_u_half<MBW>(ursrc, u_voff, (ab & 64) ? 0 : c, nchunk4, pp, u);
   };
 
   // ---- this wave's row of the transformed tile: xi = wave / 2 -> W = d[rA] + sgn d[rB]; nuh = wave % 2 -> which two of V[xi][0..3]
@@ -320,20 +254,17 @@ __global__ __launch_bounds__(RO_NTHR, 4) void conv_wino_ro_kernel(const ConvK p)
     return;
   }
 #endif
-  // ---- epilogue (conv_wino.hip): per 16-channel block(s), all sixteen positions through LDS, one thread per (channel, tile)
-  constexpr int ETILE = Gm::ETILE, ENB = ETILE / 16, EP = Gm::EP;
+  // ---- epilogue (conv_wino2.h): per 16-channel block(s), all sixteen positions through LDS; in front of the shared store pass a 16-byte
+  //      form of this kernel's own.  (The shared pass's pixel-by-pixel branch is unreachable from here -- eligibility needs W % 4 == 0 -- and
+  //      comes along only because the pass is shared.)
+  constexpr int ETILE = Gm::ETILE, EP = Gm::EP;
   float* Ml = smem;
-  const int Cout = p.G * p.cout_g;
-  const float* osp = p.osp + (int64_t)b * Cout * p.oss;
-  const float* nzp = p.nzp + (int64_t)b * p.OH * p.OW * p.nzs;
-  const float nw = p.nwp[0];
-  float* yb = p.y + ((int64_t)b * p.y_ch + p.y_coff) * p.y_h * p.y_w;
-  const float* r1b = p.r1p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r1s;
-  const float* r2b = p.r2p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r2s;
-  const int y_plane = p.y_h * p.y_w;
+  const Wino2Out out = wino2_out(p, b, 1);
+  const float *osp = out.osp, *nzp = out.nzp, *r1b = out.r1b, *r2b = out.r2b;
+  float* yb = out.yb;
+  const float nw = out.nw;
+  const int y_plane = out.y_plane;
   constexpr int EMB = Gm::EMB, ECO = 16 * EMB;
-  constexpr int EPT = ECO * ETILE / RO_NTHR;
-  typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
   constexpr int TP = ETILE / 2;                       // horizontal tile pairs per pass
   constexpr int EPT2 = ECO * TP / RO_NTHR;            // (channel, tile pair) items per thread and pass
   static_assert(ECO * TP % RO_NTHR == 0 && TLX % 2 == 0, "tile pairs");
@@ -342,166 +273,92 @@ __global__ __launch_bounds__(RO_NTHR, 4) void conv_wino_ro_kernel(const ConvK p)
   const bool quads = p.r1s <= 1 && p.r2s <= 1 && p.nzs <= 1 && (p.OW & 3) == 0 && p.y_w == p.OW && (y_plane & 3) == 0 &&
                      !(reinterpret_cast<uintptr_t>(yb) & 15) && !(p.r1s && (reinterpret_cast<uintptr_t>(r1b) & 15)) &&
                      !(p.r2s && (reinterpret_cast<uintptr_t>(r2b) & 15)) && !(p.nzs && (reinterpret_cast<uintptr_t>(nzp) & 15)) && !(p.dbg & 0x4000);
-  const bool vec2 = p.r1s <= 1 && p.r2s <= 1;
-  const bool pairs = vec2 && (p.OW & 1) == 0 && p.OW >= 2;
+  // Two passes, each over every tile, as two calls and not as a loop: inside a loop body the compiler hoists the shared store pass's
+  // thread-invariant address arithmetic in front of the first pass, across the exchange where the accumulators are still live (20 to 32 bytes
+  // of scratch on every instance of this kernel).
+  static_assert(NTILE == ETILE && MBW == 2 * EMB, "two passes, each over every tile");
+  auto pass = [&](int mb0) {
+    if (mb0 > 0) __syncthreads();                  // (the main loop ended on a barrier)
+    QOps qops[EPT2];
+    if (quads) {
 #pragma unroll
-  for (int mb0 = 0; mb0 < MBW; mb0 += EMB) {
-#pragma unroll
-    for (int th = 0; th < NTILE / ETILE; ++th) {
-      if (mb0 + th > 0) __syncthreads();
-      QOps qops[EPT2];
-      if (quads) {
-#pragma unroll
-        for (int it = 0; it < EPT2; ++it) {
-          const int e_co = (tid + it * RO_NTHR) / TP;
-          const int cgi = co0 + mb0 * 16 + e_co;
-          const int cg = g * p.cout_g + (cgi < p.cout_g ? cgi : p.cout_g - 1);
-          qops[it].os = osp[cg * p.oss]; qops[it].cs = p.csp[cg * p.css]; qops[it].cb = p.cbp[cg * p.cbs];
-          qops[it].b1 = p.b1p[cg * p.b1s]; qops[it].b2 = p.b2p[cg * p.b2s]; qops[it].sl2 = p.s2p[cg * p.s2s];
-          qops[it].cbase = cg * y_plane;
-        }
-      }
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-        for (int m2 = 0; m2 < EMB; ++m2)
-#pragma unroll
-          for (int nb = 0; nb < ENB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              Ml[((2 * wave + pp) * ECO + m2 * 16 + kq * 4 + r) * EP + nb * 16 + lr] = acc[pp][mb0 + m2][th * ENB + nb][r];
-      __syncthreads();
-      if (quads) {
-        // (uniform) two horizontally adjacent tiles per thread: the 2 x 4 output pixels leave as two 16-byte stores, the sixteen
-        // position values of both tiles come as 8-byte LDS reads, and a thread keeps ONE channel per pass (its six per-channel
-        // operands were requested before the exchange).  Measured on 64 -> 64 at 512^2: the 8-byte-per-lane form spent 200 of the
-        // kernel's 870 us here.
-#pragma unroll
-        for (int it = 0; it < EPT2; ++it) {
-          const int dp = tid + it * RO_NTHR;
-          const int e_co = dp / TP, tp = dp - e_co * TP;
-          const int e_t = (tp / (TLX / 2)) * TLX + 2 * (tp % (TLX / 2));      // first tile of the pair
-          const int e_tile = th * ETILE + e_t;
-          const int sy = oy0 + 2 * (e_tile / TLX), sx = ox0 + 2 * (e_tile % TLX);
-          float2 m[16];
-#pragma unroll
-          for (int q = 0; q < 16; ++q) m[q] = *reinterpret_cast<const float2*>(Ml + (q * ECO + e_co) * EP + e_t);
-          float yv[2][4];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            float t0[4], t1[4];
-#pragma unroll
-            for (int nu = 0; nu < 4; ++nu) {
-              const float m0 = h ? m[nu].y : m[nu].x, m1 = h ? m[4 + nu].y : m[4 + nu].x;
-              const float m2 = h ? m[8 + nu].y : m[8 + nu].x, m3 = h ? m[12 + nu].y : m[12 + nu].x;
-              t0[nu] = m0 + m1 + m2;
-              t1[nu] = m1 - m2 - m3;
-            }
-            yv[0][2 * h] = t0[0] + t0[1] + t0[2]; yv[0][2 * h + 1] = t0[1] - t0[2] - t0[3];
-            yv[1][2 * h] = t1[0] + t1[1] + t1[2]; yv[1][2 * h + 1] = t1[1] - t1[2] - t1[3];
-          }
-          const int cgi = co0 + mb0 * 16 + e_co;
-          const bool cok = cgi < p.cout_g;
-          const QOps& o = qops[it];
-          auto fin = [&](float v, float nz, float r1v, float r2v) {
-            v = v * o.os * o.cs + o.cb + o.b1;
-            v = (v > 0.f ? v : v * p.s1) * p.g1;
-            v += nz * nw + o.b2;
-            v = (v > 0.f ? v : v * o.sl2) * p.g2;
-            return v + r1v + r2v;
-          };
-          typedef float f32x4q __attribute__((ext_vector_type(4)));
-          f32x4q nz[2], r1v[2], r2v[2];
-          int ro[2];
-          bool inside[2];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = sy + i;
-            inside[i] = cok && oy < p.OH && sx < p.OW;
-            const int oyc = min(oy, p.OH - 1), oxc = min(sx, p.OW - 4);
-            ro[i] = o.cbase + oyc * p.y_w + oxc;
-            nz[i] = r1v[i] = r2v[i] = f32x4q{0.f, 0.f, 0.f, 0.f};
-            if (p.nzs) nz[i] = *reinterpret_cast<const f32x4q*>(nzp + oyc * p.OW + oxc);
-            if (p.r1s) r1v[i] = *reinterpret_cast<const f32x4q*>(r1b + ro[i]);
-            if (p.r2s) r2v[i] = *reinterpret_cast<const f32x4q*>(r2b + ro[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const f32x4q o4 = {fin(yv[i][0], nz[i][0], r1v[i][0], r2v[i][0]), fin(yv[i][1], nz[i][1], r1v[i][1], r2v[i][1]),
-                               fin(yv[i][2], nz[i][2], r1v[i][2], r2v[i][2]), fin(yv[i][3], nz[i][3], r1v[i][3], r2v[i][3])};
-            if (inside[i]) *reinterpret_cast<f32x4q*>(yb + ro[i]) = o4;
-          }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int it = 0; it < EPT; ++it) {
-        const int pair = tid + it * RO_NTHR;
-        const int e_co = pair / ETILE, e_t = pair - e_co * ETILE;
-        const int e_tile = th * ETILE + e_t;
-        const int e_tx = e_tile % TLX;
-        const int sy = oy0 + 2 * (e_tile / TLX);
-        const int sx = ox0 + 2 * e_tx;
-        float m[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) m[q] = Ml[(q * ECO + e_co) * EP + e_t];
-        float t0[4], t1[4];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-          t0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
-          t1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
-        }
-        const float yv[2][2] = {{t0[0] + t0[1] + t0[2], t0[1] - t0[2] - t0[3]}, {t1[0] + t1[1] + t1[2], t1[1] - t1[2] - t1[3]}};
+      for (int it = 0; it < EPT2; ++it) {
+        const int e_co = (tid + it * RO_NTHR) / TP;
         const int cgi = co0 + mb0 * 16 + e_co;
-        const bool cok = cgi < p.cout_g;
-        const int cg = g * p.cout_g + (cok ? cgi : p.cout_g - 1);
-        const float os = osp[cg * p.oss], cs = p.csp[cg * p.css], cb = p.cbp[cg * p.cbs];
-        const float b1 = p.b1p[cg * p.b1s], b2 = p.b2p[cg * p.b2s], sl2 = p.s2p[cg * p.s2s];
-        const int cbase = cg * y_plane;
-        auto fin = [&](float v, float nz, float r1v, float r2v) {
-          v = v * os * cs + cb + b1;
-          v = (v > 0.f ? v : v * p.s1) * p.g1;
-          v += nz * nw + b2;
-          v = (v > 0.f ? v : v * sl2) * p.g2;
-          return v + r1v + r2v;
-        };
-        if (pairs) {
-          f32x2u nz[2] = {{0.f, 0.f}, {0.f, 0.f}}, r1v[2] = {{0.f, 0.f}, {0.f, 0.f}}, r2v[2] = {{0.f, 0.f}, {0.f, 0.f}};
-          int ro[2];
-          bool inside[2];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = sy + i;
-            inside[i] = cok && oy < p.OH && sx < p.OW;
-            const int oyc = min(oy, p.OH - 1), oxc = min(sx, p.OW - 2);
-            ro[i] = cbase + oyc * p.y_w + oxc;
-            if (p.nzs) nz[i] = *reinterpret_cast<const f32x2u*>(nzp + oyc * p.OW + oxc);
-            if (p.r1s) r1v[i] = *reinterpret_cast<const f32x2u*>(r1b + ro[i]);
-            if (p.r2s) r2v[i] = *reinterpret_cast<const f32x2u*>(r2b + ro[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const f32x2u o2 = {fin(yv[i][0], nz[i][0], r1v[i][0], r2v[i][0]), fin(yv[i][1], nz[i][1], r1v[i][1], r2v[i][1])};
-            if (inside[i]) *reinterpret_cast<f32x2u*>(yb + ro[i]) = o2;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = sy + i, ox = sx;
-            if (!cok || oy >= p.OH || ox >= p.OW) continue;
-            const int ro = cbase + oy * p.y_w + ox;
-#pragma unroll
-            for (int jx = 0; jx < 2; ++jx) {
-              const int oxj = ox + jx;
-              if (oxj >= p.OW) continue;
-              const int rj = ro + jx;
-              yb[rj] = fin(yv[i][jx], nzp[(oy * p.OW + oxj) * p.nzs], r1b[rj * p.r1s], r2b[rj * p.r2s]);
-            }
-          }
-        }
+        const int cg = g * p.cout_g + (cgi < p.cout_g ? cgi : p.cout_g - 1);
+        qops[it].os = osp[cg * p.oss]; qops[it].cs = p.csp[cg * p.css]; qops[it].cb = p.cbp[cg * p.cbs];
+        qops[it].b1 = p.b1p[cg * p.b1s]; qops[it].b2 = p.b2p[cg * p.b2s]; qops[it].sl2 = p.s2p[cg * p.s2s];
+        qops[it].cbase = cg * y_plane;
       }
     }
-  }
+    wino2_exchange<MBW, NBW, ETILE, EMB, EP>(Ml, acc, mb0, 0, wave, lr, kq);
+    __syncthreads();
+    if (quads) {
+      // (uniform) two horizontally adjacent tiles per thread: the 2 x 4 output pixels leave as two 16-byte stores, the sixteen
+      // position values of both tiles come as 8-byte LDS reads, and a thread keeps ONE channel per pass (its six per-channel
+      // operands were requested before the exchange).  Measured on 64 -> 64 at 512^2: the 8-byte-per-lane form spent 200 of the
+      // kernel's 870 us here.
+#pragma unroll
+      for (int it = 0; it < EPT2; ++it) {
+        const int dp = tid + it * RO_NTHR;
+        const int e_co = dp / TP, tp = dp - e_co * TP;
+        const int e_t = (tp / (TLX / 2)) * TLX + 2 * (tp % (TLX / 2));      // first tile of the pair
+        const int sy = oy0 + 2 * (e_t / TLX), sx = ox0 + 2 * (e_t % TLX);
+        float2 m[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) m[q] = *reinterpret_cast<const float2*>(Ml + (q * ECO + e_co) * EP + e_t);
+        float yv[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          float t0[4], t1[4];
+#pragma unroll
+          for (int nu = 0; nu < 4; ++nu) {
+            const float m0 = h ? m[nu].y : m[nu].x, m1 = h ? m[4 + nu].y : m[4 + nu].x;
+            const float m2 = h ? m[8 + nu].y : m[8 + nu].x, m3 = h ? m[12 + nu].y : m[12 + nu].x;
+            t0[nu] = m0 + m1 + m2;
+            t1[nu] = m1 - m2 - m3;
+          }
+          yv[0][2 * h] = t0[0] + t0[1] + t0[2]; yv[0][2 * h + 1] = t0[1] - t0[2] - t0[3];
+          yv[1][2 * h] = t1[0] + t1[1] + t1[2]; yv[1][2 * h + 1] = t1[1] - t1[2] - t1[3];
+        }
+        const int cgi = co0 + mb0 * 16 + e_co;
+        const bool cok = cgi < p.cout_g;
+        const QOps& o = qops[it];
+        auto fin = [&](float v, float nz, float r1v, float r2v) {
+          v = v * o.os * o.cs + o.cb + o.b1;
+          v = (v > 0.f ? v : v * p.s1) * p.g1;
+          v += nz * nw + o.b2;
+          v = (v > 0.f ? v : v * o.sl2) * p.g2;
+          return v + r1v + r2v;
+        };
+        typedef float f32x4q __attribute__((ext_vector_type(4)));
+        f32x4q nz[2], r1v[2], r2v[2];
+        int ro[2];
+        bool inside[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int oy = sy + i;
+          inside[i] = cok && oy < p.OH && sx < p.OW;
+          const int oyc = min(oy, p.OH - 1), oxc = min(sx, p.OW - 4);
+          ro[i] = o.cbase + oyc * p.y_w + oxc;
+          nz[i] = r1v[i] = r2v[i] = f32x4q{0.f, 0.f, 0.f, 0.f};
+          if (p.nzs) nz[i] = *reinterpret_cast<const f32x4q*>(nzp + oyc * p.OW + oxc);
+          if (p.r1s) r1v[i] = *reinterpret_cast<const f32x4q*>(r1b + ro[i]);
+          if (p.r2s) r2v[i] = *reinterpret_cast<const f32x4q*>(r2b + ro[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const f32x4q o4 = {fin(yv[i][0], nz[i][0], r1v[i][0], r2v[i][0]), fin(yv[i][1], nz[i][1], r1v[i][1], r2v[i][1]),
+                             fin(yv[i][2], nz[i][2], r1v[i][2], r2v[i][2]), fin(yv[i][3], nz[i][3], r1v[i][3], r2v[i][3])};
+          if (inside[i]) *reinterpret_cast<f32x4q*>(yb + ro[i]) = o4;
+        }
+      }
+      return;
+    }
+    wino2_store_pass<RO_NTHR, TLX, ETILE, EMB, EP>(p, out, Ml, g, co0 + mb0 * 16, 0, oy0, ox0, 1, 0, tid);
+  };
+  pass(0);
+  pass(EMB);
 }
 
 template <int MBW, int M, int TLXV = 8>
@@ -525,10 +382,7 @@ int launch_ro(ConvK q, hipStream_t stream) {
 bool wino_ro_eligible(const ConvK& q) {
   for (int g = 0; g < q.G; ++g)
     if (q.dil[g] != 1) return false;
-  // padding = the raw-buffer range check of ONE image's descriptor (num_records = x_ch * H * W * 4 as an int; out-of-range lanes carry
-  // offset 0x7ffffff0): an image of 2 GiB or more would wrap the record count and leave the padding unbacked -- refused here
-  if ((int64_t)q.x_ch * q.H * q.W * 4 >= 0x7ffffff0ll) return false;
-  return q.cout_g > 16 && q.W % 4 == 0 && (reinterpret_cast<uintptr_t>(q.x) & 15) == 0 && ((int64_t)q.H * q.W) % 4 == 0;
+  return q.cout_g > 16 && wino2_rows_are_segments(q);
 }
 
 // m = barrier period in 8-channel sub-stages (1, 2 or 4).  (A half tile -- 64 channels x 16 tiles, 75 VGPRs, three workgroups per CU -- for the

@@ -11,43 +11,31 @@
 // group occupy dwords c0(tx) in [0, 16) -- every second one for d = 1, pairs for d = 2, ... -- so the row pitch puts the second tile row
 // 16 banks away (pitch == 8 mod 16: 24, or 40 for the 32-column rows of d = 8) and the channel pitch shifts the second channel by d
 // (pitch == d mod 32): the four 8-dword sets of an access tile the 32 banks.
-#include "conv_kernel.h"
+#include "conv_wino2.h"
 
 namespace vspconv {
 
 namespace {
 
-__device__ __forceinline__ float uload_rod(const float* base, int idx) {  // wave-uniform operand through the scalar cache
-  typedef const float __attribute__((address_space(4))) * cfp4;
-  return ((cfp4)(uintptr_t)base)[__builtin_amdgcn_readfirstlane(idx)];
-}
-
 constexpr int RD_NTHR = 512;
-constexpr int RD_IVC = 8;
+constexpr int RD_IVC = WINO2_RO_IVC;
 
 template <int MBW>
-struct RDG {
-  static constexpr int NBW = 8 / MBW;
-  static constexpr int WCO = 16 * MBW;
-  static constexpr int NTILE = 16 * NBW;
+struct RDG : Wino2Tile<MBW> {
+  using T = Wino2Tile<MBW>;
   static constexpr int TLX = 8;
-  static constexpr int TLY = NTILE / TLX;
+  static constexpr int TLY = T::NTILE / TLX;
   static constexpr int PR = 2 * TLY + 2;
   static constexpr int NLD = (PR * 8 + 63) / 64;                       // wave loads per channel plane at the widest rows (d = 8: 8 segments)
   static constexpr int PPMAX = (PR * 40 + 1 + 31) / 32 * 32 + 8;      // largest channel pitch (d = 8)
   static constexpr int LDS_P = RD_IVC * PPMAX;                        // floats per sub-stage buffer
-  static constexpr int ETILE = NTILE > 64 ? 64 : NTILE;
-  static constexpr int EMB = (MBW >= 2 && ETILE <= 32) ? 2 : 1;
-  static constexpr int EP = ETILE + 4;
-  static constexpr int LDS_M = 16 * 16 * EMB * EP;
-  static constexpr int LDS_FLOATS = 2 * LDS_P > LDS_M ? 2 * LDS_P : LDS_M;
-  static constexpr int UF = 2 * MBW;
+  static constexpr int LDS_FLOATS = 2 * LDS_P > T::LDS_M ? 2 * LDS_P : T::LDS_M;
 };
 
 template <int MBW>
 __global__ __launch_bounds__(RD_NTHR, 4) void conv_wino_rod_kernel(const ConvK p) {
   using Gm = RDG<MBW>;
-  constexpr int NBW = Gm::NBW, WCO = Gm::WCO, NTILE = Gm::NTILE, TLX = Gm::TLX, TLY = Gm::TLY, PR = Gm::PR;
+  constexpr int NBW = Gm::NBW, WCO = Gm::WCO, TLX = Gm::TLX, TLY = Gm::TLY, PR = Gm::PR;
   constexpr int LDS_P = Gm::LDS_P, UF = Gm::UF, NLD = Gm::NLD, IVC = RD_IVC, KS = 2;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Pl = smem;   // 2 x [IVC][channel pitch of this group]
@@ -56,55 +44,15 @@ __global__ __launch_bounds__(RD_NTHR, 4) void conv_wino_rod_kernel(const ConvK p
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, kq = lane >> 4;
-  // ---- work order (conv_wino.hip): region-major for shared-input dilation groups (order 4), pixel-tile-major (1) or dispatch order
+  // ---- work order (conv_wino2.h): region-major for shared-input dilation groups (order 4), pixel-tile-major (1) or dispatch order
   int b = blockIdx.z, bx = blockIdx.x, by = blockIdx.y;
   int reg_ry = -1, reg_ty = 0, reg_tx = 0;
-  if (p.wg_order == 4) {
-    constexpr int CGX = 4;
-    const int GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z, GT = GX * GY * GZ;
-    const int wgid = blockIdx.x + GX * (blockIdx.y + GY * blockIdx.z);
-    const int xcd = wgid & 7, xq = GT >> 3, xr = GT & 7;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wgid >> 3);
-    const int nb = p.tiles_y, ncg = p.tiles_x;                 // (host: bands per image, column groups per band)
-    const int per_region = GY * 8 * CGX;
-    const int region = lid / per_region, w = lid - region * per_region;
-    b = region / (nb * ncg);
-    const int rr = region - b * (nb * ncg);
-    const int band = rr / ncg, cg = rr - band * ncg;
-    const int slot = w / (GY * CGX), w2 = w - slot * (GY * CGX);
-    const int cx = w2 / GY;
-    by = w2 - cx * GY;
-    const int dg = p.dil[by / p.co_tiles];
-    reg_ry = slot % dg;
-    reg_ty = band * (8 / dg) + slot / dg;
-    reg_tx = cg * CGX + cx;
-  } else if (p.wg_order) {
-    const int GX = gridDim.x, GY = gridDim.y, GZ = gridDim.z, GT = GX * GY * GZ;
-    const int wgid = blockIdx.x + GX * (blockIdx.y + GY * blockIdx.z);
-    const int xcd = wgid & 7, xq = GT >> 3, xr = GT & 7;
-    const int lid = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (wgid >> 3);
-    const int GN = GX * GY;
-    b = lid / GN;
-    const int lrem = lid - b * GN;
-    bx = lrem / GY;
-    by = lrem - bx * GY;
-  }
+  if (p.wg_order == 4) decode_region_major(p, xcd_linear_id(), b, by, reg_ry, reg_ty, reg_tx);
+  else if (p.wg_order) decode_pixel_major(xcd_linear_id(), b, bx, by);
   const int g = by / p.co_tiles, ct = by - g * p.co_tiles;
   const int d = p.dil[g];                                       // 1, 2, 4 or 8
-  const int SH = (p.H + d - 1) / d;                             // rows of one residue class
-  const int tiles_x = (p.W + 2 * TLX - 1) / (2 * TLX), tiles_y = (SH + 2 * TLY - 1) / (2 * TLY);
-  const int per_res = tiles_x * tiles_y;
   int ry, tx_i, ty_i;
-  if (reg_ry >= 0) {
-    if (reg_ty >= tiles_y || reg_tx >= tiles_x) return;
-    ry = reg_ry; ty_i = reg_ty; tx_i = reg_tx;
-  } else {
-    if (bx >= per_res * d) return;
-    ry = bx / per_res;
-    const int tile_i = bx - ry * per_res;
-    tx_i = tile_i % tiles_x;
-    ty_i = tile_i / tiles_x;
-  }
+  if (!wino2_tile<TLX, TLY>(p, d, bx, reg_ry, reg_ty, reg_tx, ry, ty_i, tx_i)) return;
   const int oy0 = ty_i * (2 * TLY), ox0 = tx_i * (2 * TLX);     // sub-image rows, image columns
   const int hl = d > 4 ? d : 4;                                 // staged halo: whole segments
   const int SEG = (2 * TLX + 2 * hl) / 4;                       // 6 (d <= 4) or 8 segments per row
@@ -133,58 +81,20 @@ __global__ __launch_bounds__(RD_NTHR, 4) void conv_wino_rod_kernel(const ConvK p
     p_dst[i] = 1 + r * PCP + 4 * sg;
   }
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(xb), 0, p.x_ch * chw * 4, 0x00020000);   // this image (the range check compares the lane offset with size - scalar offset)
-  typedef float f32x4v __attribute__((ext_vector_type(4)));
   f32x4v preg[NLD];
-  auto load_plane = [&](int j) {
-    const int jj = j < nstage ? j : nstage - 1;
-    const int ci = jj * IVC + wave;
-    const bool chin = ci < p.Cin;                                  // (a channel past the layer: every lane offset out of range -> zeros)
-    const int soff = (chin ? ci : 0) * chw * 4;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) preg[i] = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, chin ? p_voff[i] : 0x7ffffff0, soff, 0));
-  };
+  auto load_plane = [&](int j) { wino2_load_plane<NLD>(xrsrc, p_voff, j, nstage, wave, p.Cin, chw, preg); };
   const float* wt_b = p.wtp + b * p.wt_bs;
   const float* wc_b = p.wcp + b * p.wc_bs;
   const bool affine = p.wc_cs != 0 || p.wsh_cs != 0 || p.wc_bs != 0;
-  auto commit_plane = [&](float* Pdst, int j) {
-    const int ci = j * IVC + wave;
-    const bool chok = ci < p.Cin;
-    const int cc = chok ? ci : p.Cin - 1;
-    const float st = uload_rod(wt_b, cc * p.wt_cs);
-    float sc = st, sh = 0.f;
-    if (affine) {   // (uniform for the launch) folded-BatchNorm input of the IR-SE body; the modulated layers skip two scalar loads and their address arithmetic
-      sc = uload_rod(wc_b, cc * p.wc_cs) * st;
-      sh = uload_rod(p.wshp, cc * p.wsh_cs) * st;
-    }
-    float* dst = Pdst + wave * PPITCH;
-#pragma unroll
-    for (int i = 0; i < NLD; ++i) {
-      const float shm = (((p_ok >> i) & 1u) && chok) ? sh : 0.f;   // (padding / absent channels arrive as zeros: conv_wino_ro.hip)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[p_dst[i] + e] = fmaf(preg[i][e], sc, shm);
-    }
-  };
+  auto commit_plane = [&](float* Pdst, int j) { wino2_commit_plane<NLD>(p, wt_b, wc_b, affine, Pdst, PPITCH, j, wave, p_ok, p_dst, preg); };
 
-  // ---- U fragments: [group][co tile][chunk][wave][pp 2][lane][mb MBW]; buffer loads (resource = this channel tile's slice, scalar
-  //      offset = chunk, fixed lane offset: conv_wino_ro.hip)
+  // ---- U fragments (wino2_load_u_half): resource = this channel tile's slice
   const float* utile = p.w + ((int64_t)g * p.co_tiles + ct) * nchunk4 * (8 * 64 * UF);
   const __amdgpu_buffer_rsrc_t ursrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(utile), 0, nchunk4 * (8 * 64 * UF) * 4, 0x00020000);
   const int u_voff = ((wave * 2 * 64 + lane) * MBW) * 4;
   auto load_u = [&](int c, float (&u)[UF]) {
-    const int cc = c < nchunk4 ? c : nchunk4 - 1;
-    const int soff = cc * (8 * 64 * UF * 4);
-#pragma unroll
-    for (int pp = 0; pp < 2; ++pp) {
-      if constexpr (MBW == 4) {
-        typedef float f32x4b __attribute__((ext_vector_type(4)));
-        const f32x4b a = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(ursrc, u_voff + pp * 64 * MBW * 4, soff, 0));
-        u[pp * 4 + 0] = a[0]; u[pp * 4 + 1] = a[1]; u[pp * 4 + 2] = a[2]; u[pp * 4 + 3] = a[3];
-      } else {
-        typedef float f32x2b __attribute__((ext_vector_type(2)));
-        const f32x2b a = __builtin_bit_cast(f32x2b, __builtin_amdgcn_raw_buffer_load_b64(ursrc, u_voff + pp * 64 * MBW * 4, soff, 0));
-        u[pp * 2 + 0] = a[0]; u[pp * 2 + 1] = a[1];
-      }
-    }
+    wino2_load_u_half<MBW>(ursrc, u_voff, c, nchunk4, 0, u);
+    wino2_load_u_half<MBW>(ursrc, u_voff, c, nchunk4, 1, u);
   };
 
   // ---- this wave's row of the transformed tile
@@ -267,104 +177,8 @@ __global__ __launch_bounds__(RD_NTHR, 4) void conv_wino_rod_kernel(const ConvK p
     __syncthreads();
   }
 
-  // ---- epilogue (conv_wino.hip): all sixteen positions through LDS, one thread per (channel, tile); pixels of a tile lie d apart
-  constexpr int ETILE = Gm::ETILE, ENB = ETILE / 16, EP = Gm::EP;
-  float* Ml = smem;
-  const int Cout = p.G * p.cout_g;
-  const float* osp = p.osp + (int64_t)b * Cout * p.oss;
-  const float* nzp = p.nzp + (int64_t)b * p.OH * p.OW * p.nzs;
-  const float nw = p.nwp[0];
-  float* yb = p.y + ((int64_t)b * p.y_ch + p.y_coff) * p.y_h * p.y_w;
-  const float* r1b = p.r1p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r1s;
-  const float* r2b = p.r2p + ((int64_t)b * p.res_ch + p.res_coff) * p.y_h * p.y_w * p.r2s;
-  const int y_plane = p.y_h * p.y_w;
-  constexpr int EMB = Gm::EMB, ECO = 16 * EMB;
-  constexpr int EPT = ECO * ETILE / RD_NTHR;
-  typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-  const bool pairs = d == 1 && p.r1s <= 1 && p.r2s <= 1 && (p.OW & 1) == 0 && p.OW >= 2;
-#pragma unroll
-  for (int mb0 = 0; mb0 < MBW; mb0 += EMB) {
-#pragma unroll
-    for (int th = 0; th < NTILE / ETILE; ++th) {
-      if (mb0 + th > 0) __syncthreads();
-#pragma unroll
-      for (int pp = 0; pp < 2; ++pp)
-#pragma unroll
-        for (int m2 = 0; m2 < EMB; ++m2)
-#pragma unroll
-          for (int nb = 0; nb < ENB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              Ml[((2 * wave + pp) * ECO + m2 * 16 + kq * 4 + r) * EP + nb * 16 + lr] = acc[pp][mb0 + m2][th * ENB + nb][r];
-      __syncthreads();
-#pragma unroll
-      for (int it = 0; it < EPT; ++it) {
-        const int pair = tid + it * RD_NTHR;
-        const int e_co = pair / ETILE, e_t = pair - e_co * ETILE;
-        const int e_tile = th * ETILE + e_t;
-        const int e_tx = e_tile % TLX;
-        const int sy = oy0 + 2 * (e_tile / TLX);
-        const int sx = ox0 + (e_tx % d) + 2 * d * (e_tx / d);   // first output column of the tile
-        float m[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) m[q] = Ml[(q * ECO + e_co) * EP + e_t];
-        float t0[4], t1[4];
-#pragma unroll
-        for (int nu = 0; nu < 4; ++nu) {
-          t0[nu] = m[nu] + m[4 + nu] + m[8 + nu];
-          t1[nu] = m[4 + nu] - m[8 + nu] - m[12 + nu];
-        }
-        const float yv[2][2] = {{t0[0] + t0[1] + t0[2], t0[1] - t0[2] - t0[3]}, {t1[0] + t1[1] + t1[2], t1[1] - t1[2] - t1[3]}};
-        const int cgi = co0 + mb0 * 16 + e_co;
-        const bool cok = cgi < p.cout_g;
-        const int cg = g * p.cout_g + (cok ? cgi : p.cout_g - 1);
-        const float os = osp[cg * p.oss], cs = p.csp[cg * p.css], cb = p.cbp[cg * p.cbs];
-        const float b1 = p.b1p[cg * p.b1s], b2 = p.b2p[cg * p.b2s], sl2 = p.s2p[cg * p.s2s];
-        const int cbase = cg * y_plane;
-        auto fin = [&](float v, float nz, float r1v, float r2v) {
-          v = v * os * cs + cb + b1;
-          v = (v > 0.f ? v : v * p.s1) * p.g1;
-          v += nz * nw + b2;
-          v = (v > 0.f ? v : v * sl2) * p.g2;
-          return v + r1v + r2v;
-        };
-        if (pairs) {
-          f32x2u nz[2] = {{0.f, 0.f}, {0.f, 0.f}}, r1v[2] = {{0.f, 0.f}, {0.f, 0.f}}, r2v[2] = {{0.f, 0.f}, {0.f, 0.f}};
-          int ro[2];
-          bool inside[2];
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = (sy + i) * d + ry;
-            inside[i] = cok && oy < p.OH && sx < p.OW;
-            const int oyc = min(oy, p.OH - 1), oxc = min(sx, p.OW - 2);
-            ro[i] = cbase + oyc * p.y_w + oxc;
-            if (p.nzs) nz[i] = *reinterpret_cast<const f32x2u*>(nzp + oyc * p.OW + oxc);
-            if (p.r1s) r1v[i] = *reinterpret_cast<const f32x2u*>(r1b + ro[i]);
-            if (p.r2s) r2v[i] = *reinterpret_cast<const f32x2u*>(r2b + ro[i]);
-          }
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const f32x2u o2 = {fin(yv[i][0], nz[i][0], r1v[i][0], r2v[i][0]), fin(yv[i][1], nz[i][1], r1v[i][1], r2v[i][1])};
-            if (inside[i]) *reinterpret_cast<f32x2u*>(yb + ro[i]) = o2;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const int oy = (sy + i) * d + ry, ox = sx;
-            if (!cok || oy >= p.OH || ox >= p.OW) continue;
-            const int ro = cbase + oy * p.y_w + ox;
-#pragma unroll
-            for (int jx = 0; jx < 2; ++jx) {
-              const int oxj = ox + jx * d;
-              if (oxj >= p.OW) continue;
-              const int rj = ro + jx * d;
-              yb[rj] = fin(yv[i][jx], nzp[(oy * p.OW + oxj) * p.nzs], r1b[rj * p.r1s], r2b[rj * p.r2s]);
-            }
-          }
-        }
-      }
-    }
-  }
+  // ---- epilogue (conv_wino2.h); the pixels of a tile lie d apart
+  wino2_epilogue<RD_NTHR, MBW, NBW, TLX, Gm::ETILE, Gm::EMB, Gm::EP>(p, smem, acc, b, g, co0, oy0, ox0, d, ry, tid, wave, lr, kq);
 }
 
 template <int MBW>
@@ -374,20 +188,9 @@ int launch_rod(ConvK q, hipStream_t stream) {
   const size_t lds = (size_t)Gm::LDS_FLOATS * sizeof(float);
   if (int rc = attr.ensure(reinterpret_cast<const void*>(conv_wino_rod_kernel<MBW>), (int)lds, "conv2d_winograd (row-owner, dilation groups)")) return rc;
   q.co_tiles = (q.cout_g + Gm::WCO - 1) / Gm::WCO;
-  int blocks = 0;  // the largest per-group tile count (groups with a smaller dilation exit early)
-  for (int g = 0; g < q.G; ++g) {
-    const int d = q.dil[g];
-    const int SH = (q.H + d - 1) / d;
-    const int n = ((q.W + 2 * Gm::TLX - 1) / (2 * Gm::TLX)) * ((SH + 2 * Gm::TLY - 1) / (2 * Gm::TLY)) * d;
-    blocks = n > blocks ? n : blocks;
-  }
+  int blocks = wino2_group_blocks(q, Gm::TLX, Gm::TLY);
   q.wg_order = q.H * q.W <= 1024 ? 1 : 0;
-  if (q.G >= 2 && q.x_gs == 0 && !(q.dbg & 0x800000)) {   // region-major order over bands of 8 x 2 TLY rows x 4 column tiles (conv_wino.hip)
-    q.wg_order = 4;
-    q.tiles_y = (q.H + 16 * Gm::TLY - 1) / (16 * Gm::TLY);
-    q.tiles_x = ((q.W + 2 * Gm::TLX - 1) / (2 * Gm::TLX) + 3) / 4;
-    blocks = q.tiles_y * q.tiles_x * 32;
-  }
+  if (q.G >= 2 && q.x_gs == 0 && !(q.dbg & 0x800000)) wino2_region_major(q, Gm::TLY, Gm::TLX, &blocks);
   dim3 grid((unsigned)blocks, (unsigned)(q.co_tiles * q.G), (unsigned)q.B);
   conv_wino_rod_kernel<MBW><<<grid, RD_NTHR, lds, stream>>>(q);
   return VSP_OK;
@@ -399,10 +202,7 @@ int launch_rod(ConvK q, hipStream_t stream) {
 bool wino_rod_eligible(const ConvK& q) {
   for (int g = 0; g < q.G; ++g)
     if (q.dil[g] != 1 && q.dil[g] != 2 && q.dil[g] != 4 && q.dil[g] != 8) return false;
-  // padding = the raw-buffer range check of ONE image's descriptor (num_records = x_ch * H * W * 4 as an int; out-of-range lanes carry
-  // offset 0x7ffffff0): an image of 2 GiB or more would wrap the record count and leave the padding unbacked -- refused here
-  if ((int64_t)q.x_ch * q.H * q.W * 4 >= 0x7ffffff0ll) return false;
-  return q.cout_g > 16 && q.W % 4 == 0 && (reinterpret_cast<uintptr_t>(q.x) & 15) == 0 && ((int64_t)q.H * q.W) % 4 == 0;
+  return q.cout_g > 16 && wino2_rows_are_segments(q);
 }
 
 int wino_rod_launch(ConvK q, int mbw, hipStream_t stream) { return mbw == 4 ? launch_rod<4>(q, stream) : launch_rod<2>(q, stream); }
