@@ -41,7 +41,8 @@ const char* vsp_last_error(void);
 int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
- * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item, 12 = vsp_jpeg_dec_item): lets a binding in
+ * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item, 12 = vsp_jpeg_dec_item,
+ * 13 = vsp_resample_dst): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -760,6 +761,22 @@ size_t vsp_lanczos_work_bytes(int rows, int W);
 int vsp_lanczos_resize_u8(uint8_t* out_u8, float* out_f32, const uint8_t* src, size_t src_bytes, const int32_t* coef, size_t coef_ints,
                           uint8_t* work, size_t work_bytes, const vsp_resample_item* items, const vsp_resample_item* items_dev, int n,
                           int H, int W, vsp_stream_t stream);
+
+/* The same resize for a batch whose items each have a window of their own, written into one packed buffer: item i computes the
+ * dst[i].W x dst[i].H window at (x0, y0) of its resized image and writes it as packed (H_i, W_i, 3) uint8 at byte dst[i].out_off of
+ * `out` (any byte offset: 3 W H may be odd); its intermediate rows in `work` have the stride vsp_lanczos_work_bytes(1, W_i).  Bytes
+ * of `out` outside the windows are not written.  `items` / `dst` are the tables in HOST memory, `items_dev` / `dst_dev` the same in
+ * device memory.  Checked before anything is launched: all that vsp_lanczos_resize_u8 checks, per item against its own window (a
+ * VSP_RESAMPLE_COPY item has sw == nw == W_i and sh == nh == H_i); every destination inside out_bytes; destinations ascending and
+ * disjoint.  VSP_EINVAL / VSP_ENOTSUP as there. */
+typedef struct vsp_resample_dst {
+  int64_t out_off;   /* byte offset of the item's (H, W, 3) window in `out` */
+  int32_t W, H;      /* the window: columns x0 .. x0 + W - 1 and rows y0 .. y0 + H - 1 of the resized image */
+} vsp_resample_dst;
+
+int vsp_lanczos_resize_ragged_u8(uint8_t* out, size_t out_bytes, const uint8_t* src, size_t src_bytes, const int32_t* coef, size_t coef_ints,
+                                 uint8_t* work, size_t work_bytes, const vsp_resample_item* items, const vsp_resample_item* items_dev,
+                                 const vsp_resample_dst* dst, const vsp_resample_dst* dst_dev, int n, vsp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Device-side PNG encoder: row filters + deflate of a (B, H, W, C) uint8 batch (csrc/png.hip), 8 bits per sample, C = 3 (colour type

@@ -1,7 +1,9 @@
 """Host ingest against device ingest (vspbfr_amd/resample.py, csrc/resample.hip), on sources synthesised in a temporary directory:
 
   restore    images/s of RestoreTestSet stacked on the main thread (what the inference CLIs do) and of imageio.DeviceRestoreLoader, for
-             1024^2 PNG and JPEG sources to 512^2, B = 8, each window ending in a device synchronise
+             1024^2 PNG and JPEG sources to 512^2, B = 8, each window ending in a device synchronise; for the JPEG sources also the
+             loader with decode="device" (the device JPEG decoder feeding the resize) beside decode="host", at 8 pool
+             threads and at 2 (a rank's share of 16 CPUs with 8 ranks on a node)
   train      images/s of trainset.DegradeLoader(resize="host") and (resize="device") over the same PNG sources (degradation included)
   host_split one thread: decode alone and decode + LANCZOS cover resize + crop per image (what the resize is of the host cost)
   resize     device time of one vsp_lanczos_resize_u8 call for 8 images 1024^2 -> 512^2 (both launches, upload excluded): HIP events,
@@ -9,8 +11,9 @@
   cli        the dataset loop of vspbfr_amd.restoration_metrics (tester_restore_ddpm between device synchronisations) with --ingest host
              and --ingest device over 64 pairs of 512^2 PNGs, --batch 8 --timesteps 4 --no_sample (the settings of
              profiles/metrics_cli_overhead.json; sources of the target size, so this one moves only the decode), alternating, five each
+  cli_jpg    the same loop over JPEG pairs with --ingest host, --ingest device and --ingest device --decode device
 
-    python tools/bench_ingest.py [--out profiles/ingest_bench.json] [--skip-cli]
+    python tools/bench_ingest.py [--out profiles/ingest_bench.json] [--skip-cli] [--only restore_jpg,resize,cli_jpg]
 """
 import argparse
 import json
@@ -53,7 +56,7 @@ def rate(fn, n_images, repeats=3):
     return {"images_per_s": round(statistics.median(runs), 1), "runs": [round(r, 1) for r in runs]}
 
 
-def bench_restore(root, B, size):
+def bench_restore(root, B, size, device_decode=False):
     from vspbfr_amd.imageio import DeviceRestoreLoader, RestoreTestSet
     data = RestoreTestSet(root, None, (size, size))
     n = len(data)
@@ -71,7 +74,25 @@ def bench_restore(root, B, size):
         return low
 
     assert torch.equal(host(), device())
-    return {"main_thread_stack": rate(host, n), "device_loader": rate(device, n)}
+    res = {"main_thread_stack": rate(host, n), "device_loader": rate(device, n)}
+    if device_decode:
+        def loader(threads, decode):
+            def run():
+                it = DeviceRestoreLoader(data, B, "cuda", threads=threads, decode=decode)
+                for _, low, _ in it:
+                    pass
+                torch.cuda.synchronize()
+                run.how = it.how
+                return low
+            return run
+        last = host()
+        for threads in (8, 2):
+            for decode in ("host", "device"):
+                fn = loader(threads, decode)
+                assert torch.equal(last, fn())
+                res[f"device_loader_decode_{decode}_threads_{threads}"] = rate(fn, n)
+        res["files_decoded_on_the_device"] = sum(v == "device" for v in fn.how.values())
+    return res
 
 
 def bench_train(root, B, size):
@@ -135,7 +156,8 @@ def bench_resize_call(B, src_size, size, rng):
     return res
 
 
-def bench_cli(tmp, rng, pairs=64, size=512, B=8):
+def bench_cli(tmp, rng, pairs=64, size=512, B=8, ext="png", modes=(("host", "host", None), ("device", "device", None))):
+    """modes: (name, --ingest, --decode)"""
     from PIL import Image
     from vspbfr_amd import restoration_metrics as RM
     from vspbfr_amd.diffusion import Code_diffuser
@@ -143,7 +165,7 @@ def bench_cli(tmp, rng, pairs=64, size=512, B=8):
     from vspbfr_amd.pipeline import RestorationPipeline, load_ddpm
     from vspbfr_amd.restorenet import Restoration_net
     torch.manual_seed(0)
-    ck = os.path.join(tmp, "ckpt")
+    ck = os.path.join(tmp, "ckpt_" + ext)
     os.makedirs(ck)
     torch.save({"att_mapper": Code_diffuser(timesteps=4).state_dict()}, os.path.join(ck, "code_diffuser.pt"))
     enc, dec = Encoder4Editing(50, "ir_se", Namespace(input_channel=3, stylegan_size=1024)), Generator(1024, 512, 8)
@@ -153,29 +175,32 @@ def bench_cli(tmp, rng, pairs=64, size=512, B=8):
                 "opts": {"encoder_type": "Encoder4Editing", "stylegan_size": 1024, "start_from_latent_avg": True}},
                os.path.join(ck, "psp.pt"))
     del enc, dec, sd
-    lq, hq = os.path.join(tmp, "cli_lq"), os.path.join(tmp, "cli_hq")
-    write_images(lq, pairs, size, "png", rng)
-    write_images(hq, pairs, size, "png", rng)
+    lq, hq = os.path.join(tmp, "cli_lq_" + ext), os.path.join(tmp, "cli_hq_" + ext)
+    write_images(lq, pairs, size, ext, rng)
+    write_images(hq, pairs, size, ext, rng)
     device = torch.device("cuda", 0)
     g_ema = Restoration_net(size, 512, 8).to(device).eval()
     psp = E4e_embedding(os.path.join(ck, "psp.pt"), out_size=size, size=1024, device=device, use_generator=True)
     pipe = RestorationPipeline(g_ema, psp, load_ddpm(os.path.join(ck, "code_diffuser.pt"), device=device, timesteps=4), mixing=0.5,
                                with_sample=False)
-    times = {"host": [], "device": []}
+    times = {name: [] for name, _, _ in modes}
     for rep in range(6):                       # the first of each is the warm run
-        for mode in ("host", "device"):
-            args = Namespace(batch=B, size=size, debug=False, metrics=False, ingest=mode)
+        for mode, ingest, decode in modes:
+            args = Namespace(batch=B, size=size, debug=False, metrics=False, ingest=ingest, decode=decode)
             torch.manual_seed(123)
             random.seed(123)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            RM.tester_restore_ddpm(args, pipe, lq, hq, os.path.join(tmp, f"eval_{mode}_{rep}"), "demo", device)
+            RM.tester_restore_ddpm(args, pipe, lq, hq, os.path.join(tmp, f"eval_{ext}_{mode}_{rep}"), "demo", device)
             torch.cuda.synchronize()
             if rep:
                 times[mode].append(time.perf_counter() - t0)
-    return {"what": f"{pairs} pairs of {size}^2 PNG, --batch {B} --timesteps 4 --no_sample, dataset loop between synchronisations, alternating",
-            "host_loop_s": times["host"], "device_loop_s": times["device"],
-            "host_loop_median_s": statistics.median(times["host"]), "device_loop_median_s": statistics.median(times["device"])}
+    res = {"what": f"{pairs} pairs of {size}^2 {ext.upper()}, --batch {B} --timesteps 4 --no_sample, dataset loop between synchronisations, "
+                   "alternating"}
+    for name, _, _ in modes:
+        res[f"{name}_loop_s"] = times[name]
+        res[f"{name}_loop_median_s"] = statistics.median(times[name])
+    return res
 
 
 def main():
@@ -183,7 +208,12 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--images", type=int, default=32, help="sources per format")
     ap.add_argument("--skip-cli", action="store_true")
+    ap.add_argument("--only", default=None, help="comma-separated sections: restore_png, restore_jpg, train, resize, cli, cli_jpg")
     a = ap.parse_args()
+    want = None if a.only is None else set(a.only.split(","))
+
+    def on(name):
+        return want is None or name in want
     if not torch.cuda.is_available():
         raise SystemExit("bench_ingest: no GPU")
     import PIL
@@ -193,13 +223,20 @@ def main():
            "cpus_used": len(os.sched_getaffinity(0))}
     with tempfile.TemporaryDirectory() as d:
         for ext in ("png", "jpg"):
-            write_images(os.path.join(d, ext), a.images, 1024, ext, rng)
-            res[f"restore_{ext}"] = bench_restore(os.path.join(d, ext), B, S)
-            res[f"host_split_{ext}"] = bench_host_split(os.path.join(d, ext), S)
-        res["train_png"] = bench_train(os.path.join(d, "png"), B, S)
-        res["resize_call"] = bench_resize_call(B, 1024, S, rng)
-        if not a.skip_cli:
+            if on(f"restore_{ext}") or (ext == "png" and on("train")):
+                write_images(os.path.join(d, ext), a.images, 1024, ext, rng)
+            if on(f"restore_{ext}"):
+                res[f"restore_{ext}"] = bench_restore(os.path.join(d, ext), B, S, device_decode=ext == "jpg")
+                res[f"host_split_{ext}"] = bench_host_split(os.path.join(d, ext), S)
+        if on("train"):
+            res["train_png"] = bench_train(os.path.join(d, "png"), B, S)
+        if on("resize"):
+            res["resize_call"] = bench_resize_call(B, 1024, S, rng)
+        if not a.skip_cli and on("cli"):
             res["cli"] = bench_cli(d, rng)
+        if not a.skip_cli and on("cli_jpg"):
+            res["cli_jpg"] = bench_cli(d, rng, ext="jpg", modes=(("host", "host", None), ("device", "device", None),
+                                                                 ("device_decode", "device", "device")))
     line = json.dumps(res, indent=1)
     print(line)
     if a.out:

@@ -24,6 +24,13 @@
              `effective_gb_per_s` is a floor of the traffic, not a bandwidth measurement.
 
     python tools/bench_photo.py --color_fix both [--out profiles/color_fix_bench.json]
+
+  --background   instead: FacePlan.background() (the LANCZOS-upscaled photos a group's faces are pasted into) for the 8 photos
+             of 1024 x 1536 at upscale 2 and 4, from a plan built from arrays and from one built beside a device buffer
+             (device_photos, what `restore_photos --decode device` has): HIP events around the call and the wall time up to a device
+             synchronise, median of 30 after a warm-up; the first photo is compared with Pillow's resize.
+
+    python tools/bench_photo.py --background [--out FILE]
 """
 import argparse
 import json
@@ -183,6 +190,32 @@ def bench_color_fix(photos, marks, modes, levels=5):
     return res
 
 
+def bench_background(photos, marks, upscale):
+    from PIL import Image
+    from vspbfr_amd import photo as P
+    faces = [(k, pts) for k, per in enumerate(marks) for pts in per]
+    flat = torch.from_numpy(np.concatenate([a.reshape(-1) for a in photos])).cuda()
+    plans = {"arrays": P.FacePlan(photos, faces, size=512, upscale=upscale),
+             "device_photos": P.FacePlan([a.shape[:2] for a in photos], faces, size=512, upscale=upscale, device_photos=flat)}
+    want = np.asarray(Image.fromarray(photos[0]).resize((photos[0].shape[1] * upscale, photos[0].shape[0] * upscale), Image.Resampling.LANCZOS))
+    res = {"output_photo": list(plans["arrays"].out_shape[0]), "output_mb": round(plans["arrays"].out_bytes / 1e6, 1)}
+    for name, plan in plans.items():
+        plan.upload("cuda")
+        r = events(lambda: plan.background("cuda"), n=30, warm=3)
+        del r["percent_of_pipeline_step"]
+        wall = []
+        for _ in range(30):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            plan.background("cuda")
+            torch.cuda.synchronize()
+            wall.append((time.perf_counter() - t0) * 1000)
+        r["wall_median_ms"] = round(statistics.median(wall), 3)
+        r["first_photo_equals_pillow"] = bool(np.array_equal(plan.split(plan.background("cuda"))[0].cpu().numpy(), want))
+        res[name] = r
+    return res
+
+
 def cli_setup(tmp, photos, marks):
     """random checkpoints, the photos as PNG files under tmp/photos and a PhotoRestorer at --batch 8 --timesteps 4 --no_sample: what a CLI
     loop needs besides its args -> (restorer, root, names, landmarks, device); tools/bench_jpeg.py times its loop on the same set-up"""
@@ -242,9 +275,22 @@ def main():
     ap.add_argument("--skip-cli", action="store_true")
     ap.add_argument("--antialias", action="store_true", help="the anti-aliased kernels against the bilinear ones at three face sizes")
     ap.add_argument("--color_fix", choices=["stats", "wavelet", "both"], default=None, help="the colour fix beside crop and paste")
+    ap.add_argument("--background", action="store_true", help="FacePlan.background() at upscale 2 and 4, with and without device_photos")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_photo: no GPU")
+    if a.background:
+        photos, marks = workload()
+        res = {"what": "FacePlan.background() of 8 photos of 1024 x 1536 (w x h): HIP events around the call and wall time to a device "
+                       "synchronise, median of 30", "cpus_used": len(os.sched_getaffinity(0))}
+        for s in (2, 4):
+            res[f"upscale_{s}"] = bench_background(photos, marks, s)
+        line = json.dumps(res, indent=1)
+        print(line)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return
     if a.color_fix:
         photos, marks = workload()
         res = {"what": "16 faces from 8 photos of 1024 x 1536 (w x h), S = 512, upscale 1: colour fix (DESIGN 17) beside crop and paste; HIP "

@@ -13,7 +13,7 @@ import os
 import torch  # noqa: F401
 
 from .photo import FaceAAItem, FaceItem, FaceTile  # vsp_face_item / vsp_face_tile / vsp_face_aa_item: the same arrangement for the whole-photo face path
-from .resample import ResampleItem  # vsp_resample_item: defined beside the plan that fills it, importable without the library
+from .resample import ResampleDst, ResampleItem  # vsp_resample_item / vsp_resample_dst: defined beside the plan that fills them, importable without the library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VSPBFR_HIP_LIB", os.path.join(_HERE, "lib", "libvspbfr_hip.so"))
@@ -200,6 +200,7 @@ SIGNATURES = {
     "vsp_degrade_up_f32": [_p, _p, _p, _i, _i, _i, _p],
     "vsp_pair_stats_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p],
     "vsp_lanczos_resize_u8": [_p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _i, _i, _p],
+    "vsp_lanczos_resize_ragged_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p, _i, _p],
     "vsp_png_encode_u8": [_p, C.c_size_t, _p, _p, _p, _i, _i, _i, _i, _p],
     "vsp_niqe_features_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "vsp_face_crop_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
@@ -244,7 +245,8 @@ def _load():
     if lib.vsp_abi_version() != ABI_VERSION:
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
-                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem)):
+                      (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem),
+                      (13, ResampleDst)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

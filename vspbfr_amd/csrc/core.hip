@@ -41,6 +41,7 @@ int vsp_struct_size(int which) {
     case 10: return (int)sizeof(vsp_face_aa_item);
     case 11: return (int)sizeof(vsp_jpeg_item);
     case 12: return (int)sizeof(vsp_jpeg_dec_item);
+    case 13: return (int)sizeof(vsp_resample_dst);
     default: return -1;
   }
 }

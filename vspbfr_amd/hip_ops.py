@@ -1679,6 +1679,8 @@ def lanczos_resize_u8(plan, items, coef, src, u8=True, f32=False):
     _u8(items, "items"), _u8(coef, "coef"), _u8(src, "src")
     if not (u8 or f32):
         raise RuntimeError("lanczos_resize_u8: no output asked for")
+    if plan.ragged:
+        raise RuntimeError("lanczos_resize_u8: a plan with out_sizes goes through lanczos_resize_ragged_u8")
     if items.numel() != Ct.sizeof(plan.items) or coef.numel() != 4 * plan.coef_ints or src.numel() != plan.src_bytes:
         raise RuntimeError("lanczos_resize_u8: the device sections do not have the plan's sizes")
     n, Hh, Ww = plan.n, plan.H, plan.W
@@ -1689,6 +1691,30 @@ def lanczos_resize_u8(plan, items, coef, src, u8=True, f32=False):
                                     plan.work_bytes, Ct.cast(plan.items, Ct.c_void_p), _ptr(items), n, Hh, Ww, _stream()),
           "lanczos_resize_u8")
     return out8, outf
+
+
+def lanczos_resize_ragged_u8(plan, items, coef, src, dst, out):
+    """Pillow-exact LANCZOS resize of a batch whose items each have a window of their own (vsp_lanczos_resize_ragged_u8,
+    csrc/resample.hip).  plan: a vspbfr_amd.resample.ResamplePlan built with out_sizes, whose sections `items`, `coef`, `dst` (device
+    uint8 tensors, ResamplePlan.pack's layout) were uploaded; src: the source bytes on the device; out: a flat uint8 device tensor.
+    Item i's (H_i, W_i, 3) window is written at its out_off of `out`, on the current stream; the other bytes of `out` are left alone.
+    Returns out."""
+    import ctypes as Ct
+    from .resample import ResampleDst, ResampleItem
+    _u8(items, "items"), _u8(coef, "coef"), _u8(src, "src"), _u8(dst, "dst"), _u8(out, "out")
+    if not plan.ragged:
+        raise RuntimeError("lanczos_resize_ragged_u8: the plan has no out_sizes")
+    n = plan.nk
+    if (items.numel() != n * Ct.sizeof(ResampleItem) or dst.numel() != n * Ct.sizeof(ResampleDst) or coef.numel() != 4 * plan.coef_ints
+            or src.numel() != plan.src_bytes or out.dim() != 1):
+        raise RuntimeError("lanczos_resize_ragged_u8: the device sections do not have the plan's sizes")
+    if len({t.device for t in (items, coef, src, dst, out)}) != 1:
+        raise RuntimeError("lanczos_resize_ragged_u8: the sections, the source and the output must be on one device")
+    work = torch.empty(max(plan.work_bytes // 4, 1), device=src.device, dtype=torch.int32)
+    check(lib.vsp_lanczos_resize_ragged_u8(_ptr(out), out.numel(), _ptr(src), plan.src_bytes, _ptr(coef), plan.coef_ints, _ptr(work),
+                                           plan.work_bytes, Ct.cast(plan.items, Ct.c_void_p), _ptr(items), Ct.cast(plan.dst, Ct.c_void_p),
+                                           _ptr(dst), n, _stream()), "lanczos_resize_ragged_u8")
+    return out
 
 
 def png_encode(u8, guard=0):

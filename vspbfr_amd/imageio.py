@@ -10,6 +10,8 @@ is already on the GPU.
 `DeviceRestoreLoader` is the opt-in device ingest of the same dataset (`restoration_metrics --ingest device`): only the decode stays on the
 host, on a thread pool one batch ahead; the LANCZOS resize, the crop and the normalisation run on the device (vspbfr_amd.resample,
 vsp_lanczos_resize_u8) and give the bits `RestoreTestSet.__getitem__` gives.
+With `decode="device"` (`--decode device`) baseline JPEG files are decoded on the device too (vspbfr_amd.jpeg) and the resize reads them
+where the decoder wrote them; PNG files keep Pillow's decode.
 
 `PngWriter(encode="device")` is the opt-in device encoder of the other end (`restoration_metrics --encode device`): row filters and deflate run
 on the device (vspbfr_amd.png, vsp_png_encode_u8) and the worker threads only frame and write the files; the pixels are those of the host path.
@@ -104,9 +106,18 @@ class DeviceRestoreLoader:
     """RestoreTestSet with the resize on the device: iterates over (idx, low, gts) for the items lo..hi in batches, `low` and `gts`
     (B, 3, H, W) fp32 tensors on `device` (gts None without ground truth), bit-equal to stacking `dataset[i]`.  Only the decode
     (`Image.open(...).convert("RGB")`) stays on the host, on a pool of `threads` workers, one batch ahead of the consumer; a batch
-    goes up as one pinned ragged buffer and vsp_lanczos_resize_u8 resizes, crops and normalises it (vspbfr_amd.resample)."""
+    goes up as one pinned ragged buffer and vsp_lanczos_resize_u8 resizes, crops and normalises it (vspbfr_amd.resample).
 
-    def __init__(self, dataset, batch, device, lo=0, hi=None, threads=8):
+    decode="device": the files go up as they are and baseline JPEGs are decoded on the device (vspbfr_amd.jpeg.decode_files; a PNG or
+    a JPEG the decoder refuses is decoded by Pillow on the pool and copied into its slot); the resize reads the decoder's packed
+    output where it lies (ResamplePlan(device_sources=...)), so no decoded pixel of a device-decoded file crosses PCIe.  Decode and
+    resize of the next batch run on a stream of the loader's own, whose only host synchronisation is the decoder's status read-back;
+    the consumer's stream waits on an event recorded behind the resize.  `how` maps every file read so far to its route."""
+
+    def __init__(self, dataset, batch, device, lo=0, hi=None, threads=8, decode="host"):
+        if decode not in ("host", "device"):
+            raise ValueError(f"DeviceRestoreLoader: decode {decode!r}")
+        self.decode, self.how, self._side = decode, {}, None
         self.ds, self.B, self.device = dataset, int(batch), torch.device(device)
         self.lo, self.hi = int(lo), len(dataset) if hi is None else int(hi)
         if self.B < 1 or not 0 <= self.lo <= self.hi <= len(dataset):
@@ -118,24 +129,53 @@ class DeviceRestoreLoader:
         from PIL import Image
         return np.asarray(Image.open(path).convert("RGB"), dtype=np.uint8)
 
-    def _host(self, pool, idx):
-        """host half of a batch: decode on the pool, plan and pack the ragged upload (the LQ items first, then the HQ items)"""
-        from .resample import ResamplePlan, cover_geometry
-        paths = [self.ds.lq[i] for i in idx] + ([self.ds.hq[i] for i in idx] if self.ds.hq is not None else [])
-        arrs = list(pool.map(self._decode, paths))
-        n = len(idx)
+    def _paths(self, idx):
+        return [self.ds.lq[i] for i in idx] + ([self.ds.hq[i] for i in idx] if self.ds.hq is not None else [])
+
+    def _geometry(self, paths, shapes, n):
+        """(targets, origins) of a batch whose decoded images have `shapes` = [(h, w), ...]: the LQ items first, then the HQ items"""
+        from .resample import cover_geometry
         H, W = self.ds.im_size
         targets, origins = [], []
-        for k, a in enumerate(arrs):
-            ref = arrs[n + k % n] if self.ds.hq is not None else a      # the HQ image's size decides (load_pair)
-            nw, nh, box = cover_geometry(ref.shape[1], ref.shape[0], (H, W))
-            if (nw, nh) == (ref.shape[1], ref.shape[0]) == (W, H) and a.shape[:2] != (H, W):
-                raise ValueError(f"{paths[k]}: {a.shape[1]}x{a.shape[0]} beside a ground truth of the target size (load_pair keeps both as they are)")
+        for k, (h, w) in enumerate(shapes):
+            rh, rw = shapes[n + k % n] if self.ds.hq is not None else (h, w)      # the HQ image's size decides (load_pair)
+            nw, nh, box = cover_geometry(rw, rh, (H, W))
+            if (nw, nh) == (rw, rh) == (W, H) and (h, w) != (H, W):
+                raise ValueError(f"{paths[k]}: {w}x{h} beside a ground truth of the target size (load_pair keeps both as they are)")
             targets.append((nw, nh))
             origins.append(box[:2])
-        plan = ResamplePlan(arrs, targets, origins, (H, W))
+        return targets, origins
+
+    def _host(self, pool, idx):
+        """host half of a batch: decode on the pool, plan and pack the ragged upload (the LQ items first, then the HQ items)"""
+        from .resample import ResamplePlan
+        paths = self._paths(idx)
+        arrs = list(pool.map(self._decode, paths))
+        targets, origins = self._geometry(paths, [a.shape[:2] for a in arrs], len(idx))
+        plan = ResamplePlan(arrs, targets, origins, self.ds.im_size)
         plan.pack()
         return plan
+
+    def _device(self, pool, idx):
+        """a whole batch on the loader's side stream: the files' bytes up, the device decode (host-route files on the pool), the
+        resize from the decoder's packed buffer -> (fp32 (n, 3, H, W), the event behind it).  Called on the helper thread: the stream
+        context is that thread's own, and the only thing it waits for is this stream."""
+        from . import jpeg
+        from .resample import ResamplePlan
+        paths = self._paths(idx)
+        if self._side is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        with torch.cuda.device(self.device), torch.cuda.stream(self._side):
+            packed, shapes, offsets, how = jpeg.decode_files(paths, self.device, pool=pool)
+            self.how.update(zip(paths, how))
+            targets, origins = self._geometry(paths, shapes, len(idx))
+            plan = ResamplePlan(shapes, targets, origins, self.ds.im_size, device_sources=(packed, offsets))
+            _, out = plan.run(self.device, u8=False, f32=True)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        # packed and the work buffer were allocated on the side stream: the caching allocator hands their memory to that stream
+        # alone, behind the kernels that read it, so they may be dropped here
+        return out, done
 
     def __iter__(self):
         starts = list(range(self.lo, self.hi, self.B))
@@ -143,13 +183,20 @@ class DeviceRestoreLoader:
             return
         batches = [list(range(s, min(s + self.B, self.hi))) for s in starts]
         with ThreadPoolExecutor(max_workers=self.threads) as pool, ThreadPoolExecutor(max_workers=1) as ahead:
-            nxt = ahead.submit(self._host, pool, batches[0])
+            half = self._device if self.decode == "device" else self._host
+            nxt = ahead.submit(half, pool, batches[0])
             for k, idx in enumerate(batches):
-                plan = nxt.result()
+                got = nxt.result()
                 if k + 1 < len(batches):
-                    nxt = ahead.submit(self._host, pool, batches[k + 1])
-                with torch.cuda.device(self.device):
-                    _, out = plan.run(self.device, u8=False, f32=True)
+                    nxt = ahead.submit(half, pool, batches[k + 1])
+                if self.decode == "device":
+                    out, done = got
+                    cur = torch.cuda.current_stream(self.device)
+                    cur.wait_event(done)
+                    out.record_stream(cur)          # allocated on the side stream, read on this one
+                else:
+                    with torch.cuda.device(self.device):
+                        _, out = got.run(self.device, u8=False, f32=True)
                 n = len(idx)
                 yield idx, out[:n], (out[n:] if self.ds.hq is not None else None)
 

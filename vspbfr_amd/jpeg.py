@@ -331,15 +331,20 @@ def host_pixels(data):
     return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"), dtype=np.uint8)
 
 
-def decode_batch(datas, device, sub_bytes=None, want_rounds=False):
+def decode_batch(datas, device, sub_bytes=None, want_rounds=False, pool=None):
     """File contents -> (packed uint8 device tensor of (h, w, 3) images back to back, [(h, w), ...], byte offsets, how) with how[i] in
     {"device", "host"}; with want_rounds a fifth value, the kernel's round count per file (0 for a host file).  The compressed bytes
     and one pinned block of items and tables go up on the current stream; the status words are read once, and a refused or flagged
-    file is decoded by Pillow -- whose exception, if it raises one, is the caller's -- and copied into its slot."""
+    file is decoded by Pillow -- whose exception, if it raises one, is the caller's -- and copied into its slot.  pool: an executor
+    whose map() decodes the files of the host route side by side instead of one after the other on the calling thread."""
     from . import hip_ops
     datas = [bytes(d) for d in datas]
     scans = [parse(d)[0] for d in datas]
-    host = {i: host_pixels(d) for i, (d, s) in enumerate(zip(datas, scans)) if s is None}
+    hmap = map if pool is None else pool.map
+
+    def on_host(which):
+        return dict(zip(which, hmap(host_pixels, [datas[i] for i in which])))
+    host = on_host([i for i, s in enumerate(scans) if s is None])
     sizes = [host[i].shape[:2] if s is None else (s.h, s.w) for i, s in enumerate(scans)]
     offsets = [0] * len(datas)
     for i in range(1, len(datas)):
@@ -349,7 +354,7 @@ def decode_batch(datas, device, sub_bytes=None, want_rounds=False):
     rounds = [0] * len(datas)
     dev = [i for i, s in enumerate(scans) if s is not None]
     if dev and sum(scans[i].length for i in dev) >= hip_ops.JPEG_LIMIT_BYTES:
-        host.update({i: host_pixels(datas[i]) for i in dev})
+        host.update(on_host(dev))
         dev = []
     if dev:
         comp = torch.empty(sum(scans[i].length for i in dev), dtype=torch.uint8, pin_memory=True)
@@ -367,9 +372,9 @@ def decode_batch(datas, device, sub_bytes=None, want_rounds=False):
                 words = torch.stack([status, rnd]).cpu().numpy() if want_rounds else status.cpu().numpy()[None]
             except NotImplementedError:
                 words = np.ones((1, len(dev)), dtype=np.int32)
+        host.update(on_host([i for k, i in enumerate(dev) if words[0, k]]))
         for k, i in enumerate(dev):
             if words[0, k]:
-                host[i] = host_pixels(datas[i])
                 assert host[i].shape[:2] == sizes[i]
             elif want_rounds:
                 rounds[i] = int(words[1, k])
@@ -379,10 +384,11 @@ def decode_batch(datas, device, sub_bytes=None, want_rounds=False):
     return (packed, sizes, offsets, how, rounds) if want_rounds else (packed, sizes, offsets, how)
 
 
-def decode_files(paths, device, sub_bytes=None):
-    """decode_batch over the contents of `paths` (a file that is no JPEG, a PNG for instance, takes the host decode in the same call)"""
+def decode_files(paths, device, sub_bytes=None, pool=None):
+    """decode_batch over the contents of `paths` (a file that is no JPEG, a PNG for instance, takes the host decode in the same call;
+    pool: decode_batch's)"""
     datas = []
     for p in paths:
         with open(p, "rb") as f:
             datas.append(f.read())
-    return decode_batch(datas, device, sub_bytes)
+    return decode_batch(datas, device, sub_bytes, pool=pool)

@@ -376,25 +376,18 @@ class FacePlan:
     def background(self, device):
         """The packed output photos before any face is pasted, a fresh device uint8 buffer of out_bytes: the photos themselves at upscale
         1, else each photo resized to exactly (upscale w, upscale h) -- by the device LANCZOS kernel where resample.kernel_serves takes
-        it, by PIL otherwise; both are Pillow's bytes."""
+        it, by PIL otherwise; both are Pillow's bytes.  The group is ONE ragged plan (resample.ResamplePlan with out_sizes) whose
+        source is the plan's device `photos` section and whose destinations are the photos' places in the output: one launch pair,
+        and no pixel leaves the device but those of a photo the kernel does not serve."""
         import torch
         dev = self.upload(device)
         if self.upscale == 1:
             return dev["photos"].clone()
-        from .resample import ResamplePlan, host_resize, kernel_serves
-        out = torch.empty(self.out_bytes, dtype=torch.uint8, device=device)
-        photos = self.photos
-        if self.device_photos is not None:                  # the resize takes its source from the host: one copy back for the group
-            back = self.device_photos.cpu().numpy()
-            photos = [back[o:o + 3 * h * w].reshape(h, w, 3) for o, (h, w) in zip(self.src_off, self.shapes)]
-        for a, o, (oh, ow) in zip(photos, self.out_off, self.out_shape):
-            h, w = a.shape[:2]
-            if kernel_serves(w, h, ow, oh, (0, 0, ow, oh), (oh, ow)):
-                u8, _ = ResamplePlan([a], [(ow, oh)], [(0, 0)], (oh, ow)).run(device, u8=True, f32=False)
-                out[o:o + 3 * oh * ow] = u8.reshape(-1)
-            else:
-                out[o:o + 3 * oh * ow] = torch.from_numpy(host_resize(a, ow, oh, (0, 0, ow, oh)).reshape(-1).copy()).to(device)
-        return out
+        from .resample import ResamplePlan
+        out = torch.empty(self.out_bytes, dtype=torch.uint8, device=dev["photos"].device)
+        plan = ResamplePlan(self.shapes, [(ow, oh) for oh, ow in self.out_shape], [(0, 0)] * len(self.shapes), None,
+                            device_sources=(dev["photos"], self.src_off), out_sizes=self.out_shape, out_offsets=self.out_off)
+        return plan.run_into(out)
 
     def split(self, packed):
         """the (upscale h, upscale w, 3) views of a packed output buffer, one per photo"""

@@ -1,7 +1,7 @@
 """The inference CLI with its output scored against ground truth on the device.
 
     python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
-        [--ingest host|device] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
+        [--ingest host|device [--decode host|device]] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
         [--niqe_params NPZ]
 
 `vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
@@ -44,7 +44,7 @@ def _batches(args, data, lo, hi, device):
     """(idx, low on the device, gts or None) per batch; --debug stops after 11 batches"""
     if getattr(args, "ingest", "host") == "device":
         from .imageio import DeviceRestoreLoader
-        it = DeviceRestoreLoader(data, args.batch, device, lo, hi)
+        it = DeviceRestoreLoader(data, args.batch, device, lo, hi, decode=getattr(args, "decode", None) or "host")
     else:
         it = _host_batches(args, data, lo, hi, device)
     for k, b in enumerate(it):
@@ -111,6 +111,9 @@ def main(argv=None):
     ap.add_argument("--ingest", choices=["host", "device"], default="host",
                     help="extension: host = PIL decode + LANCZOS resize + crop on the main thread (as restoration_test); device = decode on "
                          "a thread pool, resize and crop on the GPU (imageio.DeviceRestoreLoader), the same bytes")
+    ap.add_argument("--decode", choices=["host", "device"], default=None,
+                    help="extension, with --ingest device: host (the default) = PIL decodes on the thread pool; device = baseline JPEG files "
+                         "are decoded on the GPU (vspbfr_amd.jpeg) and resized where the decoder wrote them, PNG files keep PIL; the same bytes")
     ap.add_argument("--encode", choices=["host", "device"], default="host",
                     help="extension: host = PIL encodes the PNGs on the writer's threads (as restoration_test); device = row filters and deflate "
                          "on the GPU (vspbfr_amd.png), the threads frame and write; other file bytes, the same pixels")
@@ -122,6 +125,8 @@ def main(argv=None):
                     help="extension: .npz pristine model (mu_pris_param, cov_pris_param; python -m vspbfr_amd.niqe_fit); adds the no-reference "
                          "niqe column and lets a dataset without ground truth be scored by it alone")
     args = ap.parse_args(argv)
+    if args.decode is not None and args.ingest != "device":
+        ap.error("--decode only has a meaning with --ingest device")
     if not args.metrics and (args.lpips_weights or args.id_weights):
         ap.error("--lpips_weights / --id_weights only have a meaning with --metrics")
     if not args.metrics and args.niqe_params:
