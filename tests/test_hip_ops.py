@@ -1260,6 +1260,8 @@ def test_conv2d_bf16dg(H, B, Cin, Cg, Hh, Ww, dils):
         assert torch.equal(H.conv2d_packed(xd, pc, bf16=True, **kw), full)
     with pytest.raises(RuntimeError):   # an affine input shift is not served
         H.conv2d_packed(xd, pc, bf16="dg", in_scale=dev(torch.rand(Cin)), in_scale_per_sample=False, in_shift=dev(torch.randn(Cin)))
+    with pytest.raises(RuntimeError):   # nor is y one element (2 bytes) off a 4-byte boundary
+        H.conv2d_packed(xd, pc, bf16="dg", out=torch.empty(bare.numel() + 1, device=DEV, dtype=torch.bfloat16)[1:].view(bare.shape))
 
 
 def test_conv2d_bf16rv_refusals(H):

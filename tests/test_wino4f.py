@@ -125,6 +125,8 @@ def test_conv2d_winograd4f_repeatable_and_refusals(H):
     with pytest.raises(RuntimeError):
         H.conv2d_packed(dev(torch.randn(1, 64, 16, 16)), pc, in_scale=dev(torch.rand(64)), in_scale_per_sample=False,
                         in_shift=dev(torch.randn(64)), winograd=5)                                   # affine input shift
+    with pytest.raises(RuntimeError):
+        H.conv2d_packed(x, pc, out=torch.empty(x.numel() + 1, device=DEV)[1:].view(x.shape), winograd=5)   # y 4 bytes off a 16-byte boundary
     # the tuned table's fall-back is silent: the same launch without the name runs on another kernel
     y = H.conv2d_packed(dev(torch.randn(1, 64, 16, 12)), pc)
     assert y.shape == (1, 64, 16, 12)

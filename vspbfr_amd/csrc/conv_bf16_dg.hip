@@ -18,7 +18,7 @@
 // Numerics: bf16(w * s) x bf16(x) products are exact in the fp32 accumulators; the style scale is rounded INTO THE WEIGHT here (the other
 // bf16 kernels round x * s): the same number of roundings per product, another place -- tests/test_hip_ops.py::test_conv2d_bf16dg states the
 // model and checks against float64 on exactly those operands.
-#include "conv_kernel.h"
+#include "conv_items.h"
 #include "vsp_bf16.h"
 
 namespace vspconv {
@@ -51,10 +51,7 @@ __device__ unsigned long long dg_trace_buf[4 * 32];
 #define DG_STAMP(idx) do {} while (0)
 #endif
 
-struct DgPlan {
-  int nwg, J, nblk, nkeys, kx, cbk, cbk_shift;
-  int n_items[4];
-};
+using DgPlan = ItemPlan;   // (one block per group: block = group)
 
 // NST = stages of 32 input channels; FULL = the whole epilogue chain (first activation, noise, second activation) instead of scale + bias;
 // RES = residual tensors.  Compile-time: the tile loop of the common form (the SMART branch launch: demodulation only) is straight-line code --
@@ -77,9 +74,9 @@ __global__ __launch_bounds__(DG_NTHR, 2) void conv_bf16_dg_kernel(const ConvK p,
   unsigned short* yg = reinterpret_cast<unsigned short*>(p.y);
 
   for (int m = slot0; m < pl.kx * pl.nblk; m += S) {
-    const int key = xcd * pl.kx + m / pl.nblk, g = m % pl.nblk;
-    if (key >= pl.nkeys) break;
-    const int b = key / pl.J, j0 = key - b * pl.J;
+    const ItemChunk ck = item_chunk(pl, xcd, m);
+    if (ck.key >= pl.nkeys) break;
+    const int b = ck.b, j0 = ck.j0, g = ck.blk;
     const int n_it = pl.n_items[g];
     if (j0 >= n_it) continue;
     const int d = p.dil[g];
@@ -103,13 +100,6 @@ __global__ __launch_bounds__(DG_NTHR, 2) void conv_bf16_dg_kernel(const ConvK p,
       const int dst = (row * DG_ROWPX + e0) * DG_PXB + q * 8 + 1024;
       u_pk[i] = (unsigned)(q | (seg << 3) | ((live ? row : 15) << 6) | (dst << 10));
     }
-    auto item_xy = [&](int it, int& ry, int& oy0, int& X0) {
-      const int t = pl.cbk_shift >= 0 ? it >> pl.cbk_shift : it / pl.cbk;
-      const int cbi = it - t * pl.cbk;
-      ry = t & (d - 1);
-      oy0 = 8 * (t >> dl);
-      X0 = 32 * cbi;
-    };
     // one register set per stage: the loads of (next item, stage s) leave right behind the commit of (this item, stage s) -- a whole item
     // (NST commits and compute phases) between a load and its use
     u32x4d pregs[NST][2][4];
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(DG_NTHR, 2) void conv_bf16_dg_kernel(const ConvK p,
     u32x4d st_val[2] = {u32x4d{0, 0, 0, 0}, u32x4d{0, 0, 0, 0}};
     unsigned st_off[2] = {DG_OOB, DG_OOB};
     int ry, oy0, X0;
-    item_xy(j0, ry, oy0, X0);
+    item_xy(pl, j0, d, dl, ry, oy0, X0);
 #pragma unroll
     for (int s = 0; s < NST; ++s) load_stage(ry, oy0, X0, s, true);
 
@@ -224,7 +214,7 @@ __global__ __launch_bounds__(DG_NTHR, 2) void conv_bf16_dg_kernel(const ConvK p,
       const bool trace_on = wgid == 77 && it == j0 + 9 * pl.J;
 #endif
       int n_ry = 0, n_oy0 = 0, n_X0 = 0;
-      item_xy(has_next ? it + pl.J : it, n_ry, n_oy0, n_X0);
+      item_xy(pl, has_next ? it + pl.J : it, d, dl, n_ry, n_oy0, n_X0);
       f32x4 acc[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -378,28 +368,8 @@ bool bf16dg_eligible(const ConvK& q) {
 }
 
 int bf16dg_launch(const ConvK& q, bool full, hipStream_t stream) {   // full: a first / second activation or a noise term (else scale + bias only)
-  DgPlan pl{};
-  pl.nblk = q.G;
-  pl.cbk = (q.W + 31) / 32;
-  pl.cbk_shift = (pl.cbk & (pl.cbk - 1)) == 0 ? __builtin_ctz(pl.cbk) : -1;
-  int nmax = 0;
-  for (int g = 0; g < q.G; ++g) {
-    const int d = q.dil[g];
-    const int sh = (q.H + d - 1) / d;
-    pl.n_items[g] = d * ((sh + 7) / 8) * pl.cbk;
-    nmax = pl.n_items[g] > nmax ? pl.n_items[g] : nmax;
-  }
   static const int wgs_env = vsp::tune_env("VSP_BF16DG_WGS") ? atoi(vsp::tune_env("VSP_BF16DG_WGS")) : 0;
-  pl.nwg = wgs_env > 0 ? (wgs_env + 7) / 8 * 8 : 2 * vsp::kNumCU;
-  int J = pl.nwg / (q.B * pl.nblk);
-  J = J < 1 ? 1 : J;
-  if (J > (nmax + 1) / 2) J = (nmax + 1) / 2;
-  J = J < 1 ? 1 : J;
-  pl.J = J;
-  pl.nkeys = q.B * J;
-  pl.kx = (pl.nkeys + 7) / 8;
-  const int chunks = pl.nkeys * pl.nblk;
-  if (chunks < pl.nwg) pl.nwg = (chunks + 7) / 8 * 8;
+  const DgPlan pl = item_plan(q, q.G, wgs_env);
   // the SMART branch launch itself (demodulation + bias only, no residuals) runs the lean straight-line form
   const bool res = q.r1s != 0 || q.r2s != 0;
   if (q.Cin <= 32) return (full || res) ? launch_dg<1, true, true>(q, pl, stream) : launch_dg<1, false, false>(q, pl, stream);

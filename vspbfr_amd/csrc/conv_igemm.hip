@@ -37,15 +37,12 @@ static int kNumCfgs = 0;
 
 static void build_table() {
   if (kNumCfgs) return;
+  using namespace vspconv;
+  const struct { const Cfg* cfgs; int count; } units[] = {{kCfgsA, kNumA}, {kCfgsB, kNumB}, {kCfgsC, kNumC}, {kCfgsD, kNumD},
+                                                          {kCfgsE, kNumE}, {kCfgsF, kNumF}, {kCfgsG, kNumG}, {kCfgsP, kNumP}};
   int n = 0;
-  for (int i = 0; i < vspconv::kNumA && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsA[i];
-  for (int i = 0; i < vspconv::kNumB && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsB[i];
-  for (int i = 0; i < vspconv::kNumC && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsC[i];
-  for (int i = 0; i < vspconv::kNumD && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsD[i];
-  for (int i = 0; i < vspconv::kNumE && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsE[i];
-  for (int i = 0; i < vspconv::kNumF && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsF[i];
-  for (int i = 0; i < vspconv::kNumG && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsG[i];
-  for (int i = 0; i < vspconv::kNumP && n < kMaxCfgs; ++i) kCfgs[n++] = vspconv::kCfgsP[i];
+  for (const auto& u : units)
+    for (int i = 0; i < u.count && n < kMaxCfgs; ++i) kCfgs[n++] = u.cfgs[i];
   kNumCfgs = n;
 }
 
@@ -73,19 +70,26 @@ static int host_round_pitch(int n, int odd) {
   return p >= n ? p : p + 32;
 }
 
-// Fill the geometry of configuration c for problem p; returns false if it does not fit (LDS / index limits).
-static bool is_tc(const Cfg& k) { return k.name[strlen(k.name) - 1] == 't'; }
-static bool is_dg(const Cfg& k) { return k.name[strlen(k.name) - 1] == 'd'; }
-static bool is_kg(const Cfg& k) { return k.name[strlen(k.name) - 1] == 'a'; }   // conv_pipe.hip: data gradient of the dilation groups
-static bool is_fg(const Cfg& k) { const size_t n = strlen(k.name); return n >= 2 && k.name[n - 2] == 'f'; }   // conv_pipe.hip fixed geometry
+// What a configuration serves is the suffix of its name: ...t the transposed mode, ...d the dilation groups, ...a their data gradient
+// (conv_pipe.hip), ...f<x> a fixed geometry (conv_pipe.hip)
+struct CfgKind {
+  bool tc, dg, kg, fg;
+};
+static CfgKind cfg_kind(const Cfg& k) {
+  const size_t n = strlen(k.name);
+  const char last = k.name[n - 1];
+  return {last == 't', last == 'd', last == 'a', n >= 2 && k.name[n - 2] == 'f'};
+}
 
+// Fill the geometry of configuration c for problem p; returns false if it does not fit (LDS / index limits).
 static bool make_plan(const vsp_conv_params& p, int c, Plan* out) {
   const Cfg& k = kCfgs[c];
-  const bool tc = is_tc(k);
+  const CfgKind kind = cfg_kind(k);
+  const bool tc = kind.tc;
   if (tc != (p.transposed != 0)) return false;
-  const bool kg = is_kg(k);
+  const bool kg = kind.kg;
   if (kg != (p.dil_by_input_quarter != 0)) return false;
-  const bool dg = is_dg(k) || kg;   // (the data-gradient form shares the staging geometry and the weight image)
+  const bool dg = kind.dg || kg;   // (the data-gradient form shares the staging geometry and the weight image)
   if (dg) {  // four dilated branches over one input, padding = dilation (SMART / LargeConv layers)
     if (p.G != 4 || p.x_group_stride != 0 || p.stride_y != 1 || p.stride_x != 1 || p.KH != 3 || p.KW != 3) return false;
     for (int g = 0; g < 4; ++g)
@@ -99,7 +103,7 @@ static bool make_plan(const vsp_conv_params& p, int c, Plan* out) {
   if (k.PF == 3 && dg) cap = NPIX >= 512 ? 5 : 4;  // shared patch with a halo of 8: square tiles stage the fewest words
   if (twl > cap) twl = cap;
   if ((1 << twl) > NPIX) twl = ilog2_ceil(NPIX);
-  const bool fg = k.PF == 3 && is_fg(k);
+  const bool fg = k.PF == 3 && kind.fg;
   if (fg) {  // conv_pipe.hip fixed geometry (dilation-group mode): 16 x 16 pixels, dilations exactly 1, 2, 4, 8
     twl = 4;
     if (!dg || p.dil[0] != 1 || p.dil[1] != 2 || p.dil[2] != 4 || p.dil[3] != 8) return false;
@@ -158,7 +162,6 @@ static bool make_plan(const vsp_conv_params& p, int c, Plan* out) {
 // staging term.  Only relative order matters.
 static double plan_cost(const vsp_conv_params& p, const Plan& pl) {
   const Cfg& k = kCfgs[pl.cfg];
-  const int CO_T = 16 * k.MB * k.WM, NPIX = 16 * k.NB * k.WN;
   const int waves = k.WM * k.WN * k.WK;
   const double blocks = ((double)pl.tiles_x * pl.tiles_y + (pl.strip_col > 0 ? pl.strip_col + pl.strip_row : 0)) * pl.co_tiles * (pl.dg ? 1 : p.G) * p.B;
   const int cin_pad = (p.Cin + k.CK - 1) / k.CK * k.CK;
@@ -169,8 +172,6 @@ static double plan_cost(const vsp_conv_params& p, const Plan& pl) {
   const double chunks = (double)cin_pad / k.CK;
   const double stage = chunks * 2500.0;                  // barrier + global latency + LDS writes per chunk
   int per_cu = (int)(160 * 1024 / (pl.lds + 1024));
-  const int by_waves = 8 / waves * 4 / 4;  // keep <= 2 waves per SIMD per block set: 8 waves/CU when 4-wave blocks
-  (void)by_waves;
   if (per_cu > 4) per_cu = 4;
   if (per_cu < 1) per_cu = 1;
   // waves per SIMD when the CU is full
@@ -186,8 +187,6 @@ static double plan_cost(const vsp_conv_params& p, const Plan& pl) {
     const double w = occ * waves / 4.0;
     t_block = mfma_cyc * (w < 1.0 ? 1.0 : w) + stage + 0.05 * reads;
   }
-  (void)CO_T;
-  (void)NPIX;
   return full * t_block;
 }
 
@@ -229,7 +228,7 @@ static const float* slope_slot(const float* kc, float slope) {
 
 }  // namespace
 
-// Argument checks shared by vsp_conv2d_f32 and vsp_conv2d_winograd_f32; *empty = nothing to do.
+// Argument checks shared by every entry; *empty = nothing to do.
 static int validate_conv(const vsp_conv_params& p, int* x_ch_out, bool* empty, bool allow_w_bstride = false) {
   *empty = false;
   VSP_REQUIRE(p.x && p.w && p.y, "conv2d: null tensor pointer");
@@ -313,6 +312,73 @@ static int fill_convk(const vsp_conv_params& p, int x_ch, ConvK& q) {
   return VSP_OK;
 }
 
+// What every entry does once its own rules hold: the shared argument checks, the empty case, the kernel argument block, the tuning word
+// (VSP_CONV_DBG; 0 in production) and the per-input-channel operands as pointer + stride -- an absent in_scale / in_shift is a device
+// constant (1 / 0) read through stride 0.  The scale is the style scale (wt*: in_scale without in_shift) or the scale of an affine input
+// (wc*: in_scale with in_shift); bf_isc_s / bf_ish_s are the channel strides the bf16 kernels read in_scale / in_shift through.
+static int conv_front(const vsp_conv_params& p, ConvK& q, bool* empty, bool allow_w_bstride = false) {
+  int x_ch = 0;
+  if (int rc = validate_conv(p, &x_ch, empty, allow_w_bstride)) return rc;
+  if (*empty) return VSP_OK;
+  if (int rc = fill_convk(p, x_ch, q)) return rc;
+  static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;
+  q.dbg = dbg;
+  const float* kc = device_consts();   // (resolved by fill_convk)
+  const bool affine = p.in_shift != nullptr, style = p.in_scale && !affine, scaled = p.in_scale && affine;
+  q.wtp = style ? p.in_scale : kc;       q.wt_cs = style ? 1 : 0;    q.wt_bs = style ? p.in_scale_bstride : 0;
+  q.wcp = scaled ? p.in_scale : kc;      q.wc_cs = scaled ? 1 : 0;   q.wc_bs = scaled ? p.in_scale_bstride : 0;
+  q.wshp = affine ? p.in_shift : kc + 1; q.wsh_cs = affine ? 1 : 0;
+  q.bf_isc_s = p.in_scale ? 1 : 0;
+  q.bf_ish_s = affine ? 1 : 0;
+  return VSP_OK;
+}
+
+// ---- rules several entries share; `who` is the entry's message prefix
+// the first n groups: dilation 1 ... dmax (pow2: a power of two), padding = dilation
+static int require_dilation_groups(const char* who, const vsp_conv_params& p, int n, int dmax, bool pow2) {
+  for (int g = 0; g < n; ++g)
+    VSP_REQUIRE(p.dil[g] >= 1 && p.dil[g] <= dmax && (!pow2 || (p.dil[g] & (p.dil[g] - 1)) == 0) && p.pad_y[g] == p.dil[g] && p.pad_x[g] == p.dil[g],
+                "%s: group %d needs a dilation of %s and padding = dilation (got dilation %d, padding %d/%d)", who, g,
+                pow2 ? "1, 2, 4 or 8" : "1 to 64", p.dil[g], p.pad_y[g], p.pad_x[g]);
+  return VSP_OK;
+}
+
+static int require_dense_output(const char* who, const vsp_conv_params& p, bool same_size) {
+  const bool dense = p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0;
+  if (!same_size) {
+    VSP_REQUIRE(dense, "%s: dense output only", who);
+    return VSP_OK;
+  }
+  VSP_REQUIRE(dense && p.OH == p.H && p.OW == p.W, "%s: dense same-size output only: the output size must equal the input size", who);
+  return VSP_OK;
+}
+
+// (in double: the entries ask before the shared checks have bounded the factors -- exact below 2^53, and above it the answer is no anyway)
+static int require_input_under_2gib(const char* who, const vsp_conv_params& p) {
+  VSP_REQUIRE((double)(p.x_ch > 0 ? p.x_ch : p.Cin) * p.H * p.W * 4 < 2147483648.0,
+              "%s: one input image must be smaller than 2 GiB (32-bit buffer offsets)", who);
+  return VSP_OK;
+}
+
+// Transposed mode (3x3, stride 2, G = 1): normalise the ignored fields -- the launch grid runs over input positions m = 0..H, n = 0..W.
+// exact: the output is (2H+1) x (2W+1); else a larger plane is allowed (the adjoint of a stride-2 conv over an even-sized input is one
+// row / column wider; the kernel only writes the (2H+1) x (2W+1) positions, the caller zeroes the margin)
+static int normalise_transposed(const char* who, vsp_conv_params& p, bool exact) {
+  VSP_REQUIRE(p.KH == 3 && p.KW == 3 && p.G == 1, "%s: transposed mode needs a 3x3 kernel and G = 1", who);
+  VSP_REQUIRE(!p.noise && !p.res1 && !p.res2, "%s: transposed mode has no noise / residual epilogue", who);
+  const int oh = 2 * p.H + 1, ow = 2 * p.W + 1;
+  VSP_REQUIRE(exact ? (p.y_h == oh && p.y_w == ow) : (p.y_h >= oh && p.y_w >= ow), "%s: transposed output must %s (2H+1)x(2W+1)", who,
+              exact ? "be" : "hold");
+  p.stride_y = p.stride_x = 1;
+  p.dil[0] = 1;
+  p.pad_y[0] = p.pad_x[0] = 1;
+  p.OH = p.H + 1;
+  p.OW = p.W + 1;
+  p.osy = p.osx = 2;
+  p.ooy = p.oox = 0;
+  return VSP_OK;
+}
+
 // configuration index kNumCfgs (tile_hint kNumCfgs + 1) names the small-map kernel of conv_smallmap.hip
 extern "C" int vsp_conv2d_num_configs(void) {
   build_table();
@@ -327,45 +393,26 @@ extern "C" int vsp_conv2d_winograd_chunk(void) { return vspconv::wino_chunk(); }
 extern "C" int vsp_conv2d_winograd_mbw(int cout_g) { return vspconv::wino_mbw(cout_g); }
 
 extern "C" int vsp_conv2d_winograd_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
+  const char* who = "conv2d_winograd";
   VSP_REQUIRE(pp != nullptr, "conv2d_winograd: null params");
   const vsp_conv_params& p = *pp;
   VSP_REQUIRE(!p.transposed && p.G >= 1 && p.G <= 4 && p.KH == 3 && p.KW == 3 && p.stride_y == 1 && p.stride_x == 1 &&
                   p.x_group_stride == 0,
               "conv2d_winograd: only 3x3, stride 1, at most four groups over one shared input");
-  for (int g = 0; g < p.G; ++g)
-    VSP_REQUIRE((p.dil[g] == 1 || p.dil[g] == 2 || p.dil[g] == 4 || p.dil[g] == 8) && p.pad_y[g] == p.dil[g] && p.pad_x[g] == p.dil[g],
-                "conv2d_winograd: group %d needs dilation 1, 2, 4 or 8 and padding = dilation (got dilation %d, padding %d/%d)", g,
-                p.dil[g], p.pad_y[g], p.pad_x[g]);
+  if (int rc = require_dilation_groups(who, p, p.G, 8, true)) return rc;
   VSP_REQUIRE(p.io_bf16 == 0, "conv2d_winograd: fp32 activations only (io_bf16 is served by vsp_conv2d_bf16)");
   VSP_REQUIRE(p.dil_by_input_quarter == 0, "conv2d_winograd: dil_by_input_quarter is served by vsp_conv2d_f32");
-  VSP_REQUIRE(p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0, "conv2d_winograd: dense output only");
-  VSP_REQUIRE(p.OH == p.H && p.OW == p.W, "conv2d_winograd: output size must equal the input size");
+  if (int rc = require_dense_output(who, p, true)) return rc;
   VSP_REQUIRE(vsp::aligned16(p.w), "conv2d_winograd: transformed weights must be 16-byte aligned");
   VSP_REQUIRE((int64_t)16 * p.Cin * p.cout_g < ((int64_t)1 << 31), "conv2d_winograd: weight tensor too large");
-  VSP_REQUIRE((int64_t)(p.x_ch > 0 ? p.x_ch : p.Cin) * p.H * p.W * 4 < ((int64_t)1 << 31),
-              "conv2d_winograd: one input image must be smaller than 2 GiB (32-bit buffer offsets)");
-  int x_ch = 0;
-  bool empty = false;
-  if (int rc = validate_conv(p, &x_ch, &empty)) return rc;
-  if (empty) return VSP_OK;
-  ConvK q{};
-  if (int rc = fill_convk(p, x_ch, q)) return rc;
-  {
-    static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;
-    q.dbg = dbg;
-  }
-  {
-    const float* kc = device_consts();
-    const bool affine = p.in_shift != nullptr;
-    q.wtp = (p.in_scale && !affine) ? p.in_scale : kc;             q.wt_cs = (p.in_scale && !affine) ? 1 : 0;
-    q.wt_bs = (p.in_scale && !affine) ? p.in_scale_bstride : 0;
-    q.wcp = (p.in_scale && affine) ? p.in_scale : kc;              q.wc_cs = (p.in_scale && affine) ? 1 : 0;
-    q.wc_bs = (p.in_scale && affine) ? p.in_scale_bstride : 0;
-    q.wshp = affine ? p.in_shift : kc + 1;                         q.wsh_cs = affine ? 1 : 0;
-  }
+  if (int rc = require_input_under_2gib(who, p)) return rc;
   VSP_REQUIRE(p.tile_hint >= 0 && p.tile_hint <= 3, "conv2d_winograd: tile_hint names the kernel form: 0 automatic, 1 task list, 2 row owner, 3 register-resident U");
+  ConvK q{};
+  bool empty = false;
+  if (int rc = conv_front(p, q, &empty)) return rc;
+  if (empty) return VSP_OK;
   if (int rc = vspconv::wino_launch(q, p.tile_hint, vsp::as_stream(stream))) return rc;
-  return vsp::check_launch("conv2d_winograd");
+  return vsp::check_launch(who);
 }
 
 extern "C" size_t vsp_winograd4_weight_floats(int cin, int cout) { return vspconv::wino4_weight_floats(cin, cout); }
@@ -381,30 +428,25 @@ extern "C" size_t vsp_conv2d_winograd4_work_floats(const vsp_conv_params* pp) {
 }
 
 extern "C" int vsp_conv2d_winograd4_f32(const vsp_conv_params* pp, float* work, size_t work_floats, vsp_stream_t stream) {
+  const char* who = "conv2d_winograd4";
   VSP_REQUIRE(pp != nullptr && work != nullptr, "conv2d_winograd4: null params / work buffer");
   const vsp_conv_params& p = *pp;
   VSP_REQUIRE(!p.transposed && p.G == 1 && p.KH == 3 && p.KW == 3 && p.stride_y == 1 && p.stride_x == 1 && p.dil[0] == 1 &&
                   p.pad_y[0] == 1 && p.pad_x[0] == 1,
               "conv2d_winograd4: one group, 3x3, stride 1, dilation 1, padding 1");
   VSP_REQUIRE(p.io_bf16 == 0 && p.dil_by_input_quarter == 0 && p.in_shift == nullptr, "conv2d_winograd4: fp32, no affine input shift");
-  VSP_REQUIRE(p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0 && p.OH == p.H && p.OW == p.W, "conv2d_winograd4: dense same-size output");
+  if (int rc = require_dense_output(who, p, true)) return rc;
   VSP_REQUIRE(vsp::aligned16(p.w) && vsp::aligned16(work), "conv2d_winograd4: weights and work buffer must be 16-byte aligned");
   VSP_REQUIRE(work_floats >= vspconv::wino4_work_floats(p.B, p.Cin, p.H, p.W), "conv2d_winograd4: work buffer too small");
   VSP_REQUIRE((int64_t)vspconv::wino4_work_floats(1, p.Cin, p.H, p.W) * 4 < ((int64_t)1 << 40), "conv2d_winograd4: image too large");
-  int x_ch = 0;
-  bool empty = false;
-  if (int rc = validate_conv(p, &x_ch, &empty)) return rc;
-  if (empty) return VSP_OK;
   ConvK q{};
-  if (int rc = fill_convk(p, x_ch, q)) return rc;
-  {
-    static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;
-    q.dbg = dbg;
-  }
+  bool empty = false;
+  if (int rc = conv_front(p, q, &empty)) return rc;
+  if (empty) return VSP_OK;
   if (!vspconv::wino4_eligible(q))
     return vsp::fail(VSP_ENOTSUP, "conv2d_winograd4: needs Cin %% 4 == 0, H, W %% 4 == 0, dense 16-byte aligned output / noise / residual planes");
   if (int rc = vspconv::wino4_launch(q, work, p.in_scale, p.in_scale ? p.in_scale_bstride : 0, vsp::as_stream(stream))) return rc;
-  return vsp::check_launch("conv2d_winograd4");
+  return vsp::check_launch(who);
 }
 
 extern "C" size_t vsp_winograd4f_weight_floats(int cin, int cout) { return vspconv::wino4f_weight_floats(cin, cout); }
@@ -416,63 +458,43 @@ extern "C" int vsp_winograd4f_weight_f32(float* U, const float* wp, int cin, int
 }
 
 extern "C" int vsp_conv2d_winograd4f_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
+  const char* who = "conv2d_winograd4f";
   VSP_REQUIRE(pp != nullptr, "conv2d_winograd4f: null params");
   const vsp_conv_params& p = *pp;
   VSP_REQUIRE(!p.transposed && p.G >= 1 && p.G <= 4 && p.KH == 3 && p.KW == 3 && p.stride_y == 1 && p.stride_x == 1,
               "conv2d_winograd4f: 3x3, stride 1, one group or up to four dilation groups over one shared input");
-  for (int g = 0; g < p.G; ++g)
-    VSP_REQUIRE((p.dil[g] == 1 || p.dil[g] == 2 || p.dil[g] == 4 || p.dil[g] == 8) && p.pad_y[g] == p.dil[g] && p.pad_x[g] == p.dil[g],
-                "conv2d_winograd4f: dilation 1 / 2 / 4 / 8, padding = dilation");
+  if (int rc = require_dilation_groups(who, p, p.G, 8, true)) return rc;
   VSP_REQUIRE(p.io_bf16 == 0 && p.dil_by_input_quarter == 0 && p.in_shift == nullptr, "conv2d_winograd4f: fp32, no affine input shift");
-  VSP_REQUIRE(p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0 && p.OH == p.H && p.OW == p.W, "conv2d_winograd4f: dense same-size output");
+  if (int rc = require_dense_output(who, p, true)) return rc;
   VSP_REQUIRE(vsp::aligned16(p.w), "conv2d_winograd4f: weights must be 16-byte aligned");
-  int x_ch = 0;
-  bool empty = false;
-  if (int rc = validate_conv(p, &x_ch, &empty)) return rc;
-  if (empty) return VSP_OK;
   ConvK q{};
-  if (int rc = fill_convk(p, x_ch, q)) return rc;
-  {
-    static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;
-    q.dbg = dbg;
-    const float* kc = device_consts();
-    q.wtp = p.in_scale ? p.in_scale : kc;
-    q.wt_cs = p.in_scale ? 1 : 0;
-    q.wt_bs = p.in_scale ? p.in_scale_bstride : 0;
-    q.wshp = kc + 1;
-    q.wsh_cs = 0;
-  }
+  bool empty = false;
+  if (int rc = conv_front(p, q, &empty)) return rc;
+  if (empty) return VSP_OK;
   if (!vspconv::wino4f_eligible(q))
     return vsp::fail(VSP_ENOTSUP, "conv2d_winograd4f: needs Cin %% 8 == 0 (<= 512), H, W %% (4 x dilation) == 0, W >= 16, groups over one shared input, dense 16-byte aligned input / output / noise / residual planes < 2 GiB per image");
   if (int rc = vspconv::wino4f_launch(q, vsp::as_stream(stream))) return rc;
-  return vsp::check_launch("conv2d_winograd4f");
+  return vsp::check_launch(who);
 }
 
-static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, bool split, int rv = 0);   // rv: 1 = conv_bf16_rv.hip, 2 = conv_bf16_dg.hip
-extern "C" int vsp_conv2d_bf16(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, false); }
-extern "C" int vsp_conv2d_bf16x3(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, true); }
+enum Bf16Kernel { kBf16General, kBf16Split, kBf16RowVector, kBf16DilationGroups };   // conv_bf16.hip (plain, hi + lo operands), conv_bf16_rv.hip, conv_bf16_dg.hip
+static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, Bf16Kernel kern);
+extern "C" int vsp_conv2d_bf16(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, kBf16General); }
+extern "C" int vsp_conv2d_bf16x3(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, kBf16Split); }
 // the row-vector-K kernel (conv_bf16_rv.hip): same operands as vsp_conv2d_bf16 with io_bf16 = 1, its own weight order; VSP_ENOTSUP when the launch is not one it serves
-extern "C" int vsp_conv2d_bf16rv(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, false, 1); }
+extern "C" int vsp_conv2d_bf16rv(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, kBf16RowVector); }
 // the dilation-group kernel (conv_bf16_dg.hip): bf16 activations, `w` = the PACKED FP32 weights of vsp_conv2d_f32 (converted in the kernel); VSP_ENOTSUP when it does not serve the launch
-extern "C" int vsp_conv2d_bf16dg(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, false, 2); }
+extern "C" int vsp_conv2d_bf16dg(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, kBf16DilationGroups); }
 
-static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, bool split, int rv) {
+static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, Bf16Kernel kern) {
+  const char* who = "conv2d_bf16";
   VSP_REQUIRE(pp != nullptr, "conv2d_bf16: null params");
   vsp_conv_params pcopy = *pp;
   int mode = 0;
   VSP_REQUIRE(pcopy.KH == 3 && pcopy.KW == 3 && pcopy.G >= 1, "conv2d_bf16: 3x3 kernels only");
-  if (pcopy.transposed) {  // same normalisation as vsp_conv2d_f32: the grid runs over input positions m = 0..H, n = 0..W
+  if (pcopy.transposed) {
     mode = 2;
-    VSP_REQUIRE(pcopy.G == 1, "conv2d_bf16: transposed mode needs G = 1");
-    VSP_REQUIRE(!pcopy.noise && !pcopy.res1 && !pcopy.res2, "conv2d_bf16: transposed mode has no noise / residual epilogue");
-    VSP_REQUIRE(pcopy.y_h == 2 * pcopy.H + 1 && pcopy.y_w == 2 * pcopy.W + 1, "conv2d_bf16: transposed output must be (2H+1)x(2W+1)");
-    pcopy.stride_y = pcopy.stride_x = 1;
-    pcopy.dil[0] = 1;
-    pcopy.pad_y[0] = pcopy.pad_x[0] = 1;
-    pcopy.OH = pcopy.H + 1;
-    pcopy.OW = pcopy.W + 1;
-    pcopy.osy = pcopy.osx = 2;
-    pcopy.ooy = pcopy.oox = 0;
+    if (int rc = normalise_transposed(who, pcopy, true)) return rc;
   } else if (pcopy.stride_y == 2 && pcopy.stride_x == 2) {
     mode = 1;
     VSP_REQUIRE(pcopy.dil[0] == 1 && pcopy.pad_y[0] == pcopy.pad_x[0] && (pcopy.pad_y[0] == 0 || pcopy.pad_y[0] == 1),
@@ -483,94 +505,68 @@ static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, bool
   } else {
     VSP_REQUIRE(pcopy.stride_y == 1 && pcopy.stride_x == 1, "conv2d_bf16: stride must be 1 or 2");
     VSP_REQUIRE(pcopy.G <= 4 || pcopy.x_group_stride > 0, "conv2d_bf16: more than four groups need their own input slices");
-    for (int g = 0; g < (pcopy.G > 4 ? 1 : pcopy.G); ++g)
-      VSP_REQUIRE(pcopy.dil[g] >= 1 && pcopy.dil[g] <= 64 && pcopy.pad_y[g] == pcopy.dil[g] && pcopy.pad_x[g] == pcopy.dil[g],
-                  "conv2d_bf16: group %d needs padding = dilation (got dilation %d, padding %d/%d)", g, pcopy.dil[g],
-                  pcopy.pad_y[g], pcopy.pad_x[g]);
-    VSP_REQUIRE(pcopy.OH == pcopy.H && pcopy.OW == pcopy.W, "conv2d_bf16: output size must equal the input size");
+    if (int rc = require_dilation_groups(who, pcopy, pcopy.G > 4 ? 1 : pcopy.G, 64, false)) return rc;
   }
   const vsp_conv_params& p = pcopy;
-  if (mode != 2) VSP_REQUIRE(p.osy == 1 && p.osx == 1 && p.ooy == 0 && p.oox == 0, "conv2d_bf16: dense output only");
+  if (mode != 2)
+    if (int rc = require_dense_output(who, p, mode == 0)) return rc;
   VSP_REQUIRE(vsp::aligned16(p.w), "conv2d_bf16: packed weights must be 16-byte aligned");
   VSP_REQUIRE(p.Cin % 8 == 0, "conv2d_bf16: Cin must be a multiple of 8 (got %d)", p.Cin);
-  VSP_REQUIRE((int64_t)(p.x_ch > 0 ? p.x_ch : p.Cin) * p.H * p.W * 4 < ((int64_t)1 << 31),
-              "conv2d_bf16: one input image must be smaller than 2 GiB (32-bit buffer offsets)");
-  int x_ch = 0;
-  bool empty = false;
-  const bool per_image_w = p.w_bstride != 0;
-  if (per_image_w) {
-    VSP_REQUIRE(!split && rv == 0 && p.io_bf16 == 1, "conv2d_bf16: per-image weights need the general bf16 kernel with bf16 activations");
+  if (int rc = require_input_under_2gib(who, p)) return rc;
+  if (p.w_bstride != 0) {   // per-image weights
+    VSP_REQUIRE(kern == kBf16General && p.io_bf16 == 1, "conv2d_bf16: per-image weights need the general bf16 kernel with bf16 activations");
     VSP_REQUIRE(p.w_bstride > 0 && p.w_bstride % 16 == 0, "conv2d_bf16: w_bstride must be a positive multiple of 16 bytes");
     VSP_REQUIRE(!p.in_scale && !p.in_shift, "conv2d_bf16: per-image weights carry the style: in_scale / in_shift must be NULL");
     VSP_REQUIRE((p.W & 1) == 0 && (reinterpret_cast<uintptr_t>(p.x) & 3) == 0, "conv2d_bf16: per-image weights need even rows (pixel-pair staging)");
   }
-  if (int rc = validate_conv(p, &x_ch, &empty, true)) return rc;
-  if (empty) return VSP_OK;
   VSP_REQUIRE((int64_t)p.G * p.cout_g <= 65535 && p.B <= 65535, "conv2d_bf16: grid too large");
-  ConvK q{};
-  if (int rc = fill_convk(p, x_ch, q)) return rc;
-  {  // the bf16 kernel reads its prologue operands unconditionally: absent ones are device constants through stride 0
-    const float* kc = device_consts();
-    q.bf_isc_s = q.in_scale ? 1 : 0;
-    q.bf_ish_s = q.in_shift ? 1 : 0;
-    if (!q.in_scale) { q.in_scale = kc; q.in_scale_bstride = 0; }
-    if (!q.in_shift) q.in_shift = kc + 1;
-  }
-  VSP_REQUIRE(!(split && p.io_bf16), "conv2d_bf16x3: the split-precision form keeps fp32 activations (io_bf16 = 0)");
+  VSP_REQUIRE(!(kern == kBf16Split && p.io_bf16), "conv2d_bf16x3: the split-precision form keeps fp32 activations (io_bf16 = 0)");
   VSP_REQUIRE(p.io_bf16 == 0 || p.io_bf16 == 1, "conv2d_bf16: io_bf16 must be 0 or 1");
   VSP_REQUIRE(p.dil_by_input_quarter == 0, "conv2d_bf16: dil_by_input_quarter is served by vsp_conv2d_f32");
+  ConvK q{};
+  bool empty = false;
+  if (int rc = conv_front(p, q, &empty, true)) return rc;
+  if (empty) return VSP_OK;
+  // the bf16 kernels read their prologue operands unconditionally: in_scale / in_shift themselves become the resolved pointers
+  q.in_scale = p.in_shift ? q.wcp : q.wtp;
+  q.in_scale_bstride = p.in_shift ? q.wc_bs : q.wt_bs;
+  q.in_shift = q.wshp;
   q.io_bf16 = p.io_bf16;
   q.w_bs = p.w_bstride / 16;
-  {
-    static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;  // ablation builds only (VSP_BF16_ABLATE)
-    q.dbg = dbg;
+  const hipStream_t s = vsp::as_stream(stream);
+  switch (kern) {
+    case kBf16DilationGroups:
+      if (mode != 0 || !vspconv::bf16dg_eligible(q)) return VSP_ENOTSUP;
+      if (int rc = vspconv::bf16dg_launch(q, p.act1 != 0 || p.act2 != 0 || p.noise != nullptr, s)) return rc;
+      return vsp::check_launch("conv2d_bf16dg");
+    case kBf16RowVector:
+      if (mode != 0 || !vspconv::bf16rv_eligible(q)) return VSP_ENOTSUP;
+      if (int rc = vspconv::bf16rv_launch(q, p.tile_hint, s)) return rc;
+      return vsp::check_launch("conv2d_bf16rv");
+    case kBf16Split:
+      if (int rc = vspconv::bf16_launch_split(q, mode, p.tile_hint, s)) return rc;
+      return vsp::check_launch("conv2d_bf16x3");
+    case kBf16General: break;
   }
-  if (rv == 2) {
-    if (mode != 0 || !vspconv::bf16dg_eligible(q)) return VSP_ENOTSUP;
-    if (int rc = vspconv::bf16dg_launch(q, p.act1 != 0 || p.act2 != 0 || p.noise != nullptr, vsp::as_stream(stream))) return rc;
-    return vsp::check_launch("conv2d_bf16dg");
-  }
-  if (rv) {
-    if (mode != 0 || !vspconv::bf16rv_eligible(q)) return VSP_ENOTSUP;
-    if (int rc = vspconv::bf16rv_launch(q, p.tile_hint, vsp::as_stream(stream))) return rc;
-    return vsp::check_launch("conv2d_bf16rv");
-  }
-  if (split) {
-    if (int rc = vspconv::bf16_launch_split(q, mode, p.tile_hint, vsp::as_stream(stream))) return rc;
-    return vsp::check_launch("conv2d_bf16x3");
-  }
-  if (int rc = vspconv::bf16_launch(q, mode, p.tile_hint, vsp::as_stream(stream))) return rc;
-  return vsp::check_launch("conv2d_bf16");
+  if (int rc = vspconv::bf16_launch(q, mode, p.tile_hint, s)) return rc;
+  return vsp::check_launch(who);
 }
 
 extern "C" int vsp_conv2d_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
+  const char* who = "conv2d";
   VSP_REQUIRE(pp != nullptr, "conv2d: null params");
   VSP_REQUIRE(pp->io_bf16 == 0, "conv2d: fp32 activations only (io_bf16 is served by vsp_conv2d_bf16)");
   build_table();
   vsp_conv_params pcopy = *pp;
-  if (pcopy.transposed) {  // normalise the ignored fields: the launch grid runs over input positions m = 0..H, n = 0..W
-    VSP_REQUIRE(pcopy.KH == 3 && pcopy.KW == 3 && pcopy.G == 1, "conv2d: transposed mode needs a 3x3 kernel and G = 1");
-    VSP_REQUIRE(!pcopy.noise && !pcopy.res1 && !pcopy.res2, "conv2d: transposed mode has no noise / residual epilogue");
-    // (a larger output plane is allowed: the adjoint of a stride-2 conv over an even-sized input is one row / column wider; the
-    //  kernel only writes the (2H+1) x (2W+1) positions, the caller zeroes the margin)
-    VSP_REQUIRE(pcopy.y_h >= 2 * pcopy.H + 1 && pcopy.y_w >= 2 * pcopy.W + 1, "conv2d: transposed output must hold (2H+1)x(2W+1)");
-    pcopy.stride_y = pcopy.stride_x = 1;
-    pcopy.dil[0] = 1;
-    pcopy.pad_y[0] = pcopy.pad_x[0] = 1;
-    pcopy.OH = pcopy.H + 1;
-    pcopy.OW = pcopy.W + 1;
-    pcopy.osy = pcopy.osx = 2;
-    pcopy.ooy = pcopy.oox = 0;
-  }
+  if (pcopy.transposed)
+    if (int rc = normalise_transposed(who, pcopy, false)) return rc;
   const vsp_conv_params& p = pcopy;
-  int x_ch = 0;
+  if (int rc = require_input_under_2gib(who, p)) return rc;
+  VSP_REQUIRE((double)p.KH * p.KW * p.Cin * p.cout_g * 4 < 2147483648.0, "conv2d: one group's weights must be smaller than 2 GiB (32-bit buffer offsets)");
+  ConvK q{};
   bool empty = false;
-  if (int rc = validate_conv(p, &x_ch, &empty)) return rc;
+  if (int rc = conv_front(p, q, &empty)) return rc;
   if (empty) return VSP_OK;
-  VSP_REQUIRE((int64_t)x_ch * p.H * p.W * 4 < ((int64_t)1 << 31) && (int64_t)p.KH * p.KW * p.Cin * p.cout_g * 4 < ((int64_t)1 << 31),
-              "conv2d: one input image and one group's weights must each be smaller than 2 GiB (32-bit buffer offsets)");
-  const int Cout = p.G * p.cout_g;
-  (void)Cout;
   {
     // the small-map kernel: named (tile_hint kNumCfgs + 1), preferred by the tuned table (negative), or -- for a shape the table
     // does not know -- when the whole batch has at most 256 output positions against K >= 1024
@@ -578,12 +574,6 @@ extern "C" int vsp_conv2d_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
     const bool named = p.tile_hint == sm, preferred = p.tile_hint == -sm;
     const bool guess = p.tile_hint == 0 && (int64_t)p.B * p.OH * p.OW <= 256 && (int64_t)p.Cin * p.KH * p.KW >= 1024;
     if ((named || preferred || guess) && !p.dil_by_input_quarter) {
-      ConvK q{};
-      if (int rc = fill_convk(p, x_ch, q)) return rc;
-      {
-        static const int dbg = vsp::tune_env("VSP_CONV_DBG") ? atoi(vsp::tune_env("VSP_CONV_DBG")) : 0;   // tuning switches (0 in production)
-        q.dbg = dbg;
-      }
       if (vspconv::smallmap_eligible(q, p.transposed != 0)) return vspconv::smallmap_launch(q, vsp::as_stream(stream));
       VSP_REQUIRE(!named, "conv2d: configuration smallmap does not fit this problem (Cin %% 16 == 0, at most 8192 output positions, not transposed)");
     }
@@ -605,7 +595,8 @@ extern "C" int vsp_conv2d_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
       Plan pl{};
       // the fused dilation-group and the pipelined kernels are only used when named (tile_hint / tuned table); the data gradient of
       // the dilation groups exists only there: its configurations are tried in table order
-      if (p.dil_by_input_quarter ? !is_kg(kCfgs[c]) : (is_dg(kCfgs[c]) || kCfgs[c].PF == 3)) continue;
+      const CfgKind kind = cfg_kind(kCfgs[c]);
+      if (p.dil_by_input_quarter ? !kind.kg : (kind.dg || kCfgs[c].PF == 3)) continue;
       if (!make_plan(p, c, &pl)) continue;
       const double cost = p.dil_by_input_quarter ? (double)c : plan_cost(p, pl);
       if (!found || cost < best_cost) {
@@ -621,26 +612,15 @@ extern "C" int vsp_conv2d_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
   const int64_t gy = best.dg ? best.co_tiles : (int64_t)best.co_tiles * p.G;
   VSP_REQUIRE(gy <= 65535 && p.B <= 65535, "conv2d: grid too large");
 
-  ConvK q{};
-  if (int rc = fill_convk(p, x_ch, q)) return rc;
   q.tw_log2 = best.tw_log2; q.th = best.th; q.tiles_x = best.tiles_x; q.tiles_y = best.tiles_y;
   q.strip_col = best.strip_col;
   q.co_tiles = best.co_tiles;
   q.w_vec4 = (p.cout_g % 4 == 0) && (CO_T % 4 == 0) && vsp::aligned16(p.w) ? 1 : 0;
   q.ps_odd = !p.transposed && p.stride_x != 1;
-  {
-    static int dbg = -1;
-    if (dbg < 0) {
-      const char* e = vsp::tune_env("VSP_CONV_DBG");
-      dbg = e ? atoi(e) : 0;
-    }
-    q.dbg = dbg;
-  }
 
-  if (k.PF == 3) {  // conv_pipe.hip: plane pitch from the plan, per-channel input scale / shift as pointer + stride
-    const float* kc = device_consts();
+  if (k.PF == 3) {  // conv_pipe.hip: plane pitch from the plan; it reads the style scale (no input shift there: make_plan) through wc*
     q.bf_plane = best.ps;
-    q.wcp = p.in_scale ? p.in_scale : kc;      q.wc_cs = p.in_scale ? 1 : 0;  q.wc_bs = p.in_scale ? p.in_scale_bstride : 0;
+    q.wcp = q.wtp;  q.wc_cs = q.wt_cs;  q.wc_bs = q.wt_bs;
   }
   if (best.lds > 64 * 1024) {
     static vsp::LdsAttrOnce raised[kMaxCfgs];   // per configuration and device

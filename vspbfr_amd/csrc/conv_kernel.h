@@ -630,6 +630,12 @@ bool wino_rod_eligible(const ConvK& q);
 int wino_rs_launch(ConvK q, hipStream_t stream);                      // conv_wino_rs.hip: register-resident U, polyphase staging (Cin <= 64)
 bool wino_rs_eligible(const ConvK& q);
 bool wino_rs_profitable(const ConvK& q);   // conv_wino_ro.hip: row-owner form, undilated groups
+// y and the residual planes that are present are 16-byte aligned with element stride <= 1 (noise: the noise plane as well): what the
+// kernels that move them as whole 16-byte quads ask of a launch
+inline bool quad_planes_ok(const ConvK& q, bool noise) {
+  auto ok = [](const void* ptr, int stride) { return stride <= 1 && (!stride || vsp::aligned16(ptr)); };
+  return vsp::aligned16(q.y) && ok(q.r1p, q.r1s) && ok(q.r2p, q.r2s) && (!noise || ok(q.nzp, q.nzs));
+}
 // conv_wino4.hip: Winograd F(4x4,3x3) as input transform + barrier-free GEMM (deep layers)
 bool wino4_eligible(const ConvK& q);
 size_t wino4_weight_floats(int cin, int cout);

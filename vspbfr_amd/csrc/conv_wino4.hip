@@ -11,13 +11,8 @@
 //
 // Interpolation points 0, +-3/4, +-3/2, infinity (not the textbook 0, +-1, +-2): every constant of B^T and A^T is a dyadic rational
 // (exact in fp32) and the fp32 error of the whole convolution is that of the direct kernel (rms 1.55e-6, max 8.7e-6 at unit scale, K = 256; the
-// textbook points: 3.2e-6, max 4.1e-5 -- tools/wino4_points.py).  With a = 3/4, b = 3/2:
-//   B^T rows:  [a2b2, 0, -(a2+b2), 0, 1, 0]            (a2b2 = 81/64, a2+b2 = 45/16)
-//              (d4 - b2 d2) +- a (d3 - b2 d1)           (b2 = 9/4)
-//              (d4 - a2 d2) +- b (d3 - a2 d1)           (a2 = 9/16)
-//              [0, a2b2, 0, -(a2+b2), 0, 1]
-//   A^T rows:  [1, 1, 1, 1, 1, 0], [0, a, -a, b, -b, 0], [0, a2, a2, b2, b2, 0], [0, a3, -a3, b3, -b3, 1]
-//   G rows  :  [64/81, 0, 0], [-128/243, -+32/81, -8/27], [32/243, +-16/81, 8/27], [0, 0, 1]      (U = G g G^T in fp64, rounded once)
+// textbook points: 3.2e-6, max 4.1e-5 -- tools/wino4_points.py).  The matrices, the fp64 weight transform and the two fp32 transforms are
+// conv_wino4.h, shared with the fused form (conv_wino4f.hip).
 //
 // Geometry: a workgroup (12 waves) owns 64 output channels x 32 tiles (16 rows x 32 columns of one image); wave w owns the three
 // Winograd positions 3 w .. 3 w + 2 (position = 6 xi + nu) with 4 x 2 MFMA blocks each: 96 accumulator registers, one workgroup per CU
@@ -28,14 +23,12 @@
 // ([lane][p][mb]: 48-byte lane stride) an instruction touched three times the cache lines it used and the GEMM ran at 60 % pipe busy.
 // Epilogue: four passes (one 16-channel block each), the 36 position planes meet in LDS, one thread per (channel, tile) applies
 // A^T . A and the fused operand chain of the other conv kernels, 16-byte stores.
-#include "conv_kernel.h"
+#include "conv_wino4.h"
 
 namespace vspconv {
 
 namespace {
 
-constexpr float W4_A = 0.75f, W4_B = 1.5f, W4_A2 = 0.5625f, W4_B2 = 2.25f, W4_A2B2 = 1.265625f, W4_SUM2 = 2.8125f;
-constexpr float W4_A3 = 0.421875f, W4_B3 = 3.375f;
 constexpr int W4_TLX = 8, W4_TLY = 4;          // tiles of 4 x 4 outputs per workgroup: 32 columns x 16 rows
 constexpr int W4_NT = W4_TLX * W4_TLY;         // 32 tiles
 constexpr int W4_THR = 768;
@@ -50,43 +43,16 @@ __global__ __launch_bounds__(256) void wino4_weight_kernel(float* __restrict__ U
   const int ch = (int)(unit % nch);
   const int t = (int)(unit / nch);
   const int ci = 4 * ch + kq;
-  const double Gm[6][3] = {{64.0 / 81.0, 0.0, 0.0},           {-128.0 / 243.0, -32.0 / 81.0, -8.0 / 27.0}, {-128.0 / 243.0, 32.0 / 81.0, -8.0 / 27.0},
-                           {32.0 / 243.0, 16.0 / 81.0, 8.0 / 27.0}, {32.0 / 243.0, -16.0 / 81.0, 8.0 / 27.0},  {0.0, 0.0, 1.0}};
   float* dst = U + unit * (int64_t)(12 * 64 * 12) + (int64_t)lane * 4;
   for (int mb = 0; mb < 4; ++mb) {
-    const int co = 64 * t + 16 * mb + lr;
-    const bool in = ci < cin && co < cout;
-    double gk[3][3];
+    float u[36];
+    w4_weight_u(wp, cin, cout, ci, 64 * t + 16 * mb + lr, u);
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) gk[tap / 3][tap % 3] = in ? (double)wp[((int64_t)tap * cin + ci) * cout + co] : 0.0;
-    double r[6][3];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int x = 0; x < 3; ++x) r[i][x] = Gm[i][0] * gk[0][x] + Gm[i][1] * gk[1][x] + Gm[i][2] * gk[2][x];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const double u = r[i][0] * Gm[j][0] + r[i][1] * Gm[j][1] + r[i][2] * Gm[j][2];
-        const int pos = 6 * i + j;
-        dst[(int64_t)(pos / 3) * (64 * 12) + (pos % 3) * 256 + mb] = (float)u;
-      }
+    for (int pos = 0; pos < 36; ++pos) dst[(int64_t)(pos / 3) * (64 * 12) + (pos % 3) * 256 + mb] = u[pos];
   }
 }
 
 // ----------------------------------------------------------------------------------------------------- input transform: V = B^T d B
-__device__ __forceinline__ void w4_bt(const float (&d)[6], float (&o)[6]) {   // one 6-vector through B^T
-  const float e1 = fmaf(-W4_B2, d[2], d[4]), o1 = fmaf(-W4_B2, d[1], d[3]);
-  const float e2 = fmaf(-W4_A2, d[2], d[4]), o2 = fmaf(-W4_A2, d[1], d[3]);
-  o[0] = fmaf(W4_A2B2, d[0], fmaf(-W4_SUM2, d[2], d[4]));
-  o[1] = fmaf(W4_A, o1, e1);
-  o[2] = fmaf(-W4_A, o1, e1);
-  o[3] = fmaf(W4_B, o2, e2);
-  o[4] = fmaf(-W4_B, o2, e2);
-  o[5] = fmaf(W4_A2B2, d[1], fmaf(-W4_SUM2, d[3], d[5]));
-}
-
 // One workgroup (4 waves) per (image, pixel tile, 16 input channels).  The 18 x 40 patch of every channel (rows oy0 - 1 .. oy0 + 16,
 // columns ox0 - 4 .. ox0 + 35: whole 16-byte segments, inside the image or outside as a whole since W % 4 == 0) goes through LDS as
 // coalesced 16-byte loads -- the first version gathered each lane's 2 x 36 window words straight from global memory, 72 strided
@@ -346,27 +312,10 @@ __global__ __launch_bounds__(W4_THR, 3) void wino4_gemm_kernel(const ConvK p, co
       float m[36];
 #pragma unroll
       for (int q = 0; q < 36; ++q) m[q] = Ml[(q * 16 + e_co) * W4_EP + e_t];
-      // Y = A^T M A: rows (xi) first, then columns (nu)
-      float z[4][6];
+      float z[4][6], yv[4][4];
+      w4_at_rows([&](int q) { return m[q]; }, z);
 #pragma unroll
-      for (int nu = 0; nu < 6; ++nu) {
-        const float s1 = m[6 + nu] + m[12 + nu], d1 = m[6 + nu] - m[12 + nu];
-        const float s2 = m[18 + nu] + m[24 + nu], d2 = m[18 + nu] - m[24 + nu];
-        z[0][nu] = m[nu] + s1 + s2;
-        z[1][nu] = fmaf(W4_B, d2, W4_A * d1);
-        z[2][nu] = fmaf(W4_B2, s2, W4_A2 * s1);
-        z[3][nu] = fmaf(W4_B3, d2, fmaf(W4_A3, d1, m[30 + nu]));
-      }
-      float yv[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const float s1 = z[i][1] + z[i][2], d1 = z[i][1] - z[i][2];
-        const float s2 = z[i][3] + z[i][4], d2 = z[i][3] - z[i][4];
-        yv[i][0] = z[i][0] + s1 + s2;
-        yv[i][1] = fmaf(W4_B, d2, W4_A * d1);
-        yv[i][2] = fmaf(W4_B2, s2, W4_A2 * s1);
-        yv[i][3] = fmaf(W4_B3, d2, fmaf(W4_A3, d1, z[i][5]));
-      }
+      for (int i = 0; i < 4; ++i) w4_at_col(z[i], yv[i]);
       auto fin = [&](float v, float nz, float r1v, float r2v) {
         v = v * os * cs + cb + b1;
         v = (v > 0.f ? v : v * p.s1) * p.g1;
@@ -403,11 +352,7 @@ bool wino4_eligible(const ConvK& q) {
   if (q.H % 4 != 0 || q.W % 4 != 0 || q.W < 16 || q.H < 8) return false;
   if (q.y_w != q.OW || q.y_h != q.OH) return false;
   if (reinterpret_cast<uintptr_t>(q.x) & 15) return false;
-  if ((reinterpret_cast<uintptr_t>(q.y) & 15) || (q.r1s > 1) || (q.r2s > 1) || (q.nzs > 1)) return false;
-  if ((q.r1s && (reinterpret_cast<uintptr_t>(q.r1p) & 15)) || (q.r2s && (reinterpret_cast<uintptr_t>(q.r2p) & 15)) ||
-      (q.nzs && (reinterpret_cast<uintptr_t>(q.nzp) & 15)))
-    return false;
-  return true;
+  return quad_planes_ok(q, true);
 }
 
 size_t wino4_weight_floats(int cin, int cout) {

@@ -21,7 +21,7 @@
 // Operand traffic per CU and k-step (2304 pipe cycles): U 18 KB + windows 4 x 6.1 KB = 18.5 B/clk from L2 (the pair's GEMM: 24).
 //
 //   U4F [co half (32)][k-step][pp 18][lane 64][4]      lane = (kq, lr): ci = 4 ks + kq; element e: position 2 pp + (e >> 1), co = 32 half + 16 (e & 1) + lr
-#include "conv_kernel.h"
+#include "conv_wino4.h"
 #include <type_traits>
 #include <cstdio>
 
@@ -33,7 +33,6 @@ typedef float f32x4f __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4f __attribute__((__vector_size__(4 * sizeof(unsigned))));
 typedef float f32x2f __attribute__((ext_vector_type(2)));
 
-constexpr float FA = 0.75f, FB = 1.5f, FA2 = 0.5625f, FB2 = 2.25f, FA2B2 = 1.265625f, FSUM2 = 2.8125f, FA3 = 0.421875f, FB3 = 3.375f;
 constexpr int F4_THR = 256;
 constexpr int F4_SLAB = 18 * 64 * 4;          // floats of one (half, k-step) slab in HBM
 constexpr int F4_SLABL = 5 * F4_THR * 4;      // floats of one LDS ring slot: five 16-byte chunks per thread (the last half-round lands in the slot's tail)
@@ -57,25 +56,8 @@ __global__ __launch_bounds__(256) void wino4f_weight_kernel(float* __restrict__ 
   const int ks = (int)(unit % nks);
   const int half = (int)(unit / nks);
   const int ci = 4 * ks + kq;
-  const double Gm[6][3] = {{64.0 / 81.0, 0.0, 0.0},           {-128.0 / 243.0, -32.0 / 81.0, -8.0 / 27.0}, {-128.0 / 243.0, 32.0 / 81.0, -8.0 / 27.0},
-                           {32.0 / 243.0, 16.0 / 81.0, 8.0 / 27.0}, {32.0 / 243.0, -16.0 / 81.0, 8.0 / 27.0},  {0.0, 0.0, 1.0}};
   float u[2][36];
-  for (int cb = 0; cb < 2; ++cb) {
-    const int co = 32 * half + 16 * cb + lr;
-    const bool in = ci < cin && co < cout;
-    double gk[3][3];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) gk[tap / 3][tap % 3] = in ? (double)wp[((int64_t)tap * cin + ci) * cout + co] : 0.0;
-    double r[6][3];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int x = 0; x < 3; ++x) r[i][x] = Gm[i][0] * gk[0][x] + Gm[i][1] * gk[1][x] + Gm[i][2] * gk[2][x];
-#pragma unroll
-    for (int i = 0; i < 6; ++i)
-#pragma unroll
-      for (int j = 0; j < 6; ++j) u[cb][6 * i + j] = (float)(r[i][0] * Gm[j][0] + r[i][1] * Gm[j][1] + r[i][2] * Gm[j][2]);
-  }
+  for (int cb = 0; cb < 2; ++cb) w4_weight_u(wp, cin, cout, ci, 32 * half + 16 * cb + lr, u[cb]);
   f32x4f* dst = reinterpret_cast<f32x4f*>(U + unit * (int64_t)F4_SLAB) + lane;
 #pragma unroll
   for (int pp = 0; pp < 18; ++pp) dst[pp * 64] = f32x4f{u[0][2 * pp], u[1][2 * pp], u[0][2 * pp + 1], u[1][2 * pp + 1]};
@@ -178,8 +160,8 @@ __device__ __forceinline__ void f4_body(const ConvK& p, const F4Plan& pl, float*
   const int it0 = slot * pl.J, it1 = min(pl.items, it0 + pl.J);
   const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w) + (int64_t)grp * pl.nco2 * nks * F4_SLAB, 0, pl.nco2 * nks * F4_SLAB * 4, 0x00020000);
   lds_f4* const Ul4 = (lds_f4*)(lds_f*)smem;
-  // constant pairs of B^T (conv_wino4.hip header): C1 = (-b2, -a2), C2 = (-(a2 + b2), a2 b2), C3 = (a, b)
-  const f32x2f C1 = {-FB2, -FA2}, C2 = {-FSUM2, FA2B2}, C3 = {FA, FB};
+  // constant pairs of B^T (conv_wino4.h): C1 = (-b2, -a2), C2 = (-(a2 + b2), a2 b2), C3 = (a, b)
+  const f32x2f C1 = {-W4_B2, -W4_A2}, C2 = {-W4_SUM2, W4_A2B2}, C3 = {W4_A, W4_B};
 
   for (int it = it0; it < it1; ++it) {
 #ifdef VSP_F4_TRACE
@@ -320,7 +302,7 @@ __device__ __forceinline__ void f4_body(const ConvK& p, const F4Plan& pl, float*
     auto colpass = [&](auto Ic, f32x2f (&T)[6][3]) {
       constexpr int i = decltype(Ic)::value;
       const f32x2f c1 = C1, c3 = C3;
-      const float fs = -FSUM2, fab = FA2B2;
+      const float fs = -W4_SUM2, fab = W4_A2B2;
       f32x2f e12, o12, v12, v34;
       if constexpr (D >= 1) {
         // LDS loader: the pairs are (d0, d1), (d2, d3), (d4, d5) -- (V0, V5) = a2b2 (d0, d1) - (a2 + b2) (d2, d3) + (d4, d5) is two packed FMAs as well
@@ -579,20 +561,12 @@ __device__ __forceinline__ void f4_body(const ConvK& p, const F4Plan& pl, float*
             }
           }
           float z[4][6];
-#pragma unroll
-          for (int nu = 0; nu < 6; ++nu) {
-            const float m0 = accr(nu, cb, r), m1 = accr(6 + nu, cb, r), m2 = accr(12 + nu, cb, r), m3 = accr(18 + nu, cb, r), m4 = accr(24 + nu, cb, r),
-                        m5 = accr(30 + nu, cb, r);
-            const float s1 = m1 + m2, d1 = m1 - m2, s2 = m3 + m4, d2 = m3 - m4;
-            z[0][nu] = m0 + s1 + s2;
-            z[1][nu] = fmaf(FB, d2, FA * d1);
-            z[2][nu] = fmaf(FB2, s2, FA2 * s1);
-            z[3][nu] = fmaf(FB3, d2, fmaf(FA3, d1, m5));
-          }
+          w4_at_rows([&](int pos) { return accr(pos, cb, r); }, z);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            const float s1 = z[i][1] + z[i][2], d1 = z[i][1] - z[i][2], s2 = z[i][3] + z[i][4], d2 = z[i][3] - z[i][4];
-            f32x4f o4 = {z[i][0] + s1 + s2, fmaf(FB, d2, FA * d1), fmaf(FB2, s2, FA2 * s1), fmaf(FB3, d2, fmaf(FA3, d1, z[i][5]))};
+            float yi[4];
+            w4_at_col(z[i], yi);
+            f32x4f o4 = {yi[0], yi[1], yi[2], yi[3]};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               float v = fmaf(o4[e], et[0], et[1]);
@@ -666,10 +640,7 @@ bool wino4f_eligible(const ConvK& q) {
   if (q.y_w != q.OW || q.y_h != q.OH) return false;
   if (q.wshp != nullptr && q.wsh_cs != 0) return false;
   if (reinterpret_cast<uintptr_t>(q.x) & 15) return false;
-  if ((reinterpret_cast<uintptr_t>(q.y) & 15) || (q.r1s > 1) || (q.r2s > 1) || (q.nzs > 1)) return false;
-  if ((q.r1s && (reinterpret_cast<uintptr_t>(q.r1p) & 15)) || (q.r2s && (reinterpret_cast<uintptr_t>(q.r2p) & 15)) ||
-      (q.nzs && (reinterpret_cast<uintptr_t>(q.nzp) & 15)))
-    return false;
+  if (!quad_planes_ok(q, true)) return false;
   if ((int64_t)q.Cin * q.H * q.W * 4 >= 0x7fffff00ll || (int64_t)q.cout_g * q.y_h * q.y_w * 4 >= 0x7fffff00ll) return false;
   if ((int64_t)q.G * ((q.cout_g + 31) / 32) * (q.Cin / 4) * F4_SLAB * 4 >= 0x7fffff00ll) return false;
   return true;

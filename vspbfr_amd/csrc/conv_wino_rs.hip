@@ -19,7 +19,7 @@
 // The plain layers are served as "groups" of 16 channels with d = 1: every block stages the patch and computes its V again -- the
 // price of keeping U in registers -- which the LDS (25 % busy) and the VALU (two operations per MFMA) have room for.
 // U is the fragment order of vsp_winograd_weight_f32 (weight_pack.hip); epilogue chain and operands are those of conv_wino.hip.
-#include "conv_kernel.h"
+#include "conv_items.h"
 
 namespace vspconv {
 
@@ -37,14 +37,8 @@ constexpr int RS_LDS_FLOATS = RS_RING + RS_XCH + RS_TAB;
 constexpr int RS_NLD = 4;                     // 16-byte segments per thread and stage (8 planes x <= 120 segments)
 constexpr unsigned RS_OOB = 0x7fffffffu;      // lane offset past every buffer: the load returns zeros (padding, absent channels)
 
-struct RsPlan {
-  int nwg;          // workgroups launched (multiple of 8)
-  int J;            // chunks per (image, block): chunk j owns items j, j + J, ...
-  int nblk, bpg;    // blocks = G * bpg, 16-channel blocks per group
-  int nkeys, kx;    // keys = (image, chunk) pairs; keys per XCD
-  int cbk;          // column blocks of 32 per image row
-  int cbk_shift;    // log2(cbk) when it is a power of two, else -1
-  int n_items[4];   // items of a block of group g: d * row blocks * cbk
+struct RsPlan : ItemPlan {
+  int bpg;            // 16-channel blocks per group: nblk = G * bpg
   int mbw, nct, nch;  // U layout (weight_pack.hip): 16-channel blocks per unit, units per group, k-steps
 };
 
@@ -90,9 +84,9 @@ __global__ __launch_bounds__(RS_NTHR, 2) void conv_wino_rs_kernel(const ConvK p,
 #endif
 
   for (int m = slot0; m < pl.kx * pl.nblk; m += S) {
-    const int key = xcd * pl.kx + m / pl.nblk, blk = m % pl.nblk;
-    if (key >= pl.nkeys) break;
-    const int b = key / pl.J, j0 = key - b * pl.J;
+    const ItemChunk ck = item_chunk(pl, xcd, m);
+    if (ck.key >= pl.nkeys) break;
+    const int b = ck.b, j0 = ck.j0, blk = ck.blk;
     const int g = blk / pl.bpg, cb = blk - g * pl.bpg;
     const int n_it = pl.n_items[g];
     if (j0 >= n_it) continue;
@@ -125,14 +119,6 @@ __global__ __launch_bounds__(RS_NTHR, 2) void conv_wino_rs_kernel(const ConvK p,
     // the four words of a segment: consecutive (d = 1), alternating strips (d = 2), one strip each (d >= 4)
     const int dlt1 = d == 1 ? 1 : SW, dlt2 = d == 1 ? 2 : (d == 2 ? 1 : 2 * SW), dlt3 = d == 1 ? 3 : (d == 2 ? SW + 1 : 3 * SW);
 
-    // ---- item geometry: item i -> column block i % cbk, t = i / cbk -> row residue t % d, row block t / d
-    auto item_xy = [&](int it, int& ry, int& oy0, int& X0) {
-      const int t = pl.cbk_shift >= 0 ? it >> pl.cbk_shift : it / pl.cbk;
-      const int cbi = it - t * pl.cbk;
-      ry = t & (d - 1);
-      oy0 = 8 * (t >> dl);
-      X0 = 32 * cbi;
-    };
     auto slot_voff = [&](int i, int ry, int oy0, int X0) -> unsigned {
       const int row = s_pk[i] & 15, seg = (s_pk[i] >> 4) & 15, pln = (s_pk[i] >> 8) & 7;
       const int sr = oy0 - 1 + row, iy = sr * d + ry, ix = X0 + 4 * seg - HL;
@@ -143,7 +129,7 @@ __global__ __launch_bounds__(RS_NTHR, 2) void conv_wino_rs_kernel(const ConvK p,
     struct ItemGeo { int mode, base, ry, oy0, X0; };   // mode 0: no item (padding marker), 1: interior, 2: border (per-segment validity)
     auto item_geo = [&](int it, bool exists) -> ItemGeo {
       ItemGeo gq;
-      item_xy(it, gq.ry, gq.oy0, gq.X0);
+      item_xy(pl, it, d, dl, gq.ry, gq.oy0, gq.X0);
       const bool interior = gq.oy0 >= 1 && (gq.oy0 + 8) * d + gq.ry < p.H && gq.X0 - HL >= 0 && gq.X0 + 32 + HL <= p.W;
       gq.mode = exists ? (interior ? 1 : 2) : 0;
       gq.base = ((gq.oy0 * d + gq.ry) * p.W + gq.X0) * 4;
@@ -467,9 +453,7 @@ bool wino_rs_eligible(const ConvK& q) {
   if ((int64_t)q.Cin * q.H * q.W * 4 >= ((int64_t)1 << 30)) return false;   // (lane offsets carry the channel: the padding marker lies above every offset)
   if ((int64_t)q.G * q.cout_g * q.y_h * q.y_w * 4 >= ((int64_t)1 << 31) || (int64_t)q.OH * q.OW * 4 >= ((int64_t)1 << 31)) return false;
   // the output (and residual) rows leave as 16-byte quads
-  if (q.y_w % 4 != 0 || ((int64_t)q.y_h * q.y_w) % 4 != 0 || (reinterpret_cast<uintptr_t>(q.y) & 15) != 0 || q.r1s > 1 || q.r2s > 1 ||
-      (q.r1s && (reinterpret_cast<uintptr_t>(q.r1p) & 15)) || (q.r2s && (reinterpret_cast<uintptr_t>(q.r2p) & 15)))
-    return false;
+  if (q.y_w % 4 != 0 || ((int64_t)q.y_h * q.y_w) % 4 != 0 || !quad_planes_ok(q, false)) return false;   // (the noise is read by words)
   for (int g = 0; g < q.G; ++g)
     if (q.dil[g] != 1 && q.dil[g] != 2 && q.dil[g] != 4 && q.dil[g] != 8) return false;
   return true;
@@ -483,30 +467,10 @@ bool wino_rs_profitable(const ConvK& q) {
 }
 
 int wino_rs_launch(ConvK q, hipStream_t stream) {
+  static const int wgs_env = vsp::tune_env("VSP_WINO_RS_WGS") ? atoi(vsp::tune_env("VSP_WINO_RS_WGS")) : 0;
   RsPlan pl{};
   pl.bpg = (q.cout_g + 15) / 16;
-  pl.nblk = q.G * pl.bpg;
-  pl.cbk = (q.W + 31) / 32;
-  pl.cbk_shift = (pl.cbk & (pl.cbk - 1)) == 0 ? __builtin_ctz(pl.cbk) : -1;
-  int nmax = 0;
-  for (int g = 0; g < q.G; ++g) {
-    const int d = q.dil[g];
-    const int sh = (q.H + d - 1) / d;
-    pl.n_items[g] = d * ((sh + 7) / 8) * pl.cbk;
-    nmax = pl.n_items[g] > nmax ? pl.n_items[g] : nmax;
-  }
-  static const int wgs_env = vsp::tune_env("VSP_WINO_RS_WGS") ? atoi(vsp::tune_env("VSP_WINO_RS_WGS")) : 0;
-  pl.nwg = wgs_env > 0 ? (wgs_env + 7) / 8 * 8 : 2 * vsp::kNumCU;
-  // chunks per (image, block): about one chunk per workgroup slot, at least ~2 items per chunk, keys a multiple of 8 when they fill the XCDs
-  int J = pl.nwg / (q.B * pl.nblk);
-  J = J < 1 ? 1 : J;
-  if (J > (nmax + 1) / 2) J = (nmax + 1) / 2;
-  J = J < 1 ? 1 : J;
-  pl.J = J;
-  pl.nkeys = q.B * J;
-  pl.kx = (pl.nkeys + 7) / 8;
-  const int chunks = pl.nkeys * pl.nblk;
-  if (chunks < pl.nwg) pl.nwg = (chunks + 7) / 8 * 8;
+  static_cast<ItemPlan&>(pl) = item_plan(q, q.G * pl.bpg, wgs_env);
   pl.mbw = wino_mbw(q.cout_g);
   pl.nct = (q.cout_g + 16 * pl.mbw - 1) / (16 * pl.mbw);
   pl.nch = (q.Cin + 3) / 4;
