@@ -42,7 +42,7 @@ int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
  * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item, 12 = vsp_jpeg_dec_item,
- * 13 = vsp_resample_dst): lets a binding in
+ * 13 = vsp_resample_dst, 14 = vsp_png_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -813,6 +813,50 @@ size_t vsp_png_segment_bound(int rows, int W, int C);
 size_t vsp_png_bound(int H, int W, int C);
 int vsp_png_encode_u8(uint8_t* out, size_t out_capacity, int32_t* seg_bytes, uint32_t* seg_adler, const uint8_t* src, int B, int H, int W,
                       int C, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Device-side PNG encoder for whole photos: a ragged batch of packed (h, w, C) uint8 images of any width (csrc/png.hip, DESIGN 21;
+ * tests/png_ragged_ref.py restates it, the device output equals it byte for byte).  Filters, tokens, codes, the stored-block rule,
+ * the empty stored block behind a non-final segment and the Adler parts are those of vsp_png_encode_u8 above; what differs is the cut:
+ *
+ *   segments   image i's filtered stream, n = h (1 + C w) bytes, is cut into segments of VSP_PNG_RAGGED_SEG_BYTES bytes, the last one
+ *              shorter: ceil(n / VSP_PNG_RAGGED_SEG_BYTES) of them.  A boundary may fall inside a row, inside a pixel, on a filter-type
+ *              byte or right behind one; a run of equal bytes is cut there.  So the files of this entry differ in bytes from those of
+ *              vsp_png_encode_u8 for the same pixels; both are valid PNG streams of those pixels
+ *   items      given twice: in host memory, checked before anything is launched, and the same table in device memory.  seg0 = the
+ *              segments of the items before (item 0: 0), row0 = the rows of the items before
+ *   work       vsp_png_ragged_work_bytes(segments, rows of the call) bytes, 4-byte aligned: global segment j's slot at byte
+ *              j * VSP_PNG_RAGGED_SLOT_BYTES, then int32 seg_bytes[segments], then one filter-type byte per row
+ *   out        image i's zlib payload, its segments back to back, at out + out_off, idat_bytes[i] bytes long (at most
+ *              vsp_png_ragged_image_bound(h, w, C) = n + 10 per segment); no byte behind it is written.  out_off need not be aligned
+ *   seg_adler  [2 j], [2 j + 1] of global segment j, as above
+ * Three launches on the caller's stream, no host synchronisation.  VSP_EINVAL, nothing launched: a null or misaligned pointer, C not 1
+ * or 3, n < 0, a size below 1, an image that leaves `src` or starts below the end of the one before it, an output range (out_off, the
+ * image bound) that leaves `out` or starts below the end of the one before it, a wrong seg0 or row0, a `work` too small.
+ * VSP_ENOTSUP, nothing launched: C w above VSP_PNG_RAGGED_MAX_ROW_BYTES, src, out or work of 2 GiB or more, more than
+ * VSP_PNG_RAGGED_MAX_IMAGES images or VSP_PNG_RAGGED_MAX_SEGMENTS segments.  n = 0 returns VSP_OK.  The size helpers return 0 for
+ * arguments outside the limits.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_PNG_RAGGED_SEG_BYTES 24576          /* <= 8 x 3073, 48 bytes per thread of 512, a stored block below 65536 */
+#define VSP_PNG_RAGGED_SLOT_BYTES 24588         /* SEG_BYTES + 10, rounded up to a dword */
+#define VSP_PNG_RAGGED_MAX_ROW_BYTES (1 << 20)  /* C w */
+#define VSP_PNG_RAGGED_MAX_IMAGES 4096
+#define VSP_PNG_RAGGED_MAX_SEGMENTS 65535       /* 1.5 GiB of filtered bytes per call */
+
+typedef struct vsp_png_item {
+  int64_t src_off;   /* byte offset of the (h, w, C) image in `src`, rows of C w bytes without padding */
+  int64_t out_off;   /* byte offset of its zlib payload in `out` */
+  int32_t h, w;
+  int32_t seg0;      /* index of its first segment among all segments of the call */
+  int32_t row0;      /* index of its first row among all rows of the call */
+} vsp_png_item;
+
+int vsp_png_ragged_segments(int H, int W, int C);
+size_t vsp_png_ragged_image_bound(int H, int W, int C);
+size_t vsp_png_ragged_work_bytes(int64_t segments, int64_t rows);
+int vsp_png_encode_ragged_u8(uint8_t* out, size_t out_bytes, int32_t* idat_bytes, uint32_t* seg_adler, uint8_t* work, size_t work_bytes,
+                             const uint8_t* src, size_t src_bytes, const vsp_png_item* items, const vsp_png_item* items_dev, int n, int C,
+                             vsp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * No-reference quality: the NIQE features (Mittal, Soundararajan, Bovik 2013) of B uint8 RGB images (B, H, W, 3), one launch,

@@ -110,6 +110,10 @@ class JpegItem(C.Structure):
     _fields_ = [("src_off", C.c_int64), ("out_off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("interval0", C.c_int32), ("pad_", C.c_int32)]
 
 
+class PngItem(C.Structure):                  # vsp_png_item
+    _fields_ = [("src_off", C.c_int64), ("out_off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("seg0", C.c_int32), ("row0", C.c_int32)]
+
+
 class JpegDecItem(C.Structure):
     _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("work_off", C.c_int64)] + [
         (n, C.c_int32) for n in ("in_len", "h", "w", "subsampling", "restart", "interval0")]
@@ -202,6 +206,8 @@ SIGNATURES = {
     "vsp_lanczos_resize_u8": [_p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _i, _i, _p],
     "vsp_lanczos_resize_ragged_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p, _i, _p],
     "vsp_png_encode_u8": [_p, C.c_size_t, _p, _p, _p, _i, _i, _i, _i, _p],
+    "vsp_png_ragged_segments": [_i, _i, _i],
+    "vsp_png_encode_ragged_u8": [_p, C.c_size_t, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _i, _p],
     "vsp_niqe_features_u8": [_p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "vsp_face_crop_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
     "vsp_face_paste_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p, C.c_size_t, _p, _p, _i, _p],
@@ -219,6 +225,7 @@ _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C
           "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i],
           "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i], "vsp_lanczos_work_bytes": [_i, _i],
           "vsp_png_segment_bound": [_i, _i, _i], "vsp_png_bound": [_i, _i, _i],
+          "vsp_png_ragged_image_bound": [_i, _i, _i], "vsp_png_ragged_work_bytes": [_i64, _i64],
           "vsp_niqe_work_bytes": [_i, _i, _i, _i],
           "vsp_jpeg_interval_bound": [_i, _i], "vsp_jpeg_image_bound": [_i, _i, _i, _i],
           "vsp_jpeg_decode_work_bytes": [_i, _i, _i, _i, _i, _i]}
@@ -246,7 +253,7 @@ def _load():
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
                       (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem),
-                      (13, ResampleDst)):
+                      (13, ResampleDst), (14, PngItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -42,6 +42,7 @@ int vsp_struct_size(int which) {
     case 11: return (int)sizeof(vsp_jpeg_item);
     case 12: return (int)sizeof(vsp_jpeg_dec_item);
     case 13: return (int)sizeof(vsp_resample_dst);
+    case 14: return (int)sizeof(vsp_png_item);
     default: return -1;
   }
 }

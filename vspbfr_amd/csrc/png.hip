@@ -13,6 +13,8 @@
 //   bits      per-chunk bit counts, a prefix sum, then every token is or-ed into the LDS bit buffer (two threads may share a dword there)
 //   store     the finished buffer goes to the segment's slot as plain dword stores; byte count and Adler parts beside it
 // The bit buffer reuses the LDS of the raw rows.  Static LDS only (below 64 KB); no scratch: every dynamically indexed array is in LDS.
+// Everything from `tokens` on is compress_segment(), which the ragged encoder for whole photos (further down: three kernels, segments of
+// VSP_PNG_RAGGED_SEG_BYTES bytes instead of rows) calls on filtered bytes it rebuilds from global memory.
 #include "vsp_common.h"
 
 namespace {
@@ -186,10 +188,12 @@ __device__ __forceinline__ void or_bits(uint32_t* buf, int off, uint64_t v) {
   if (hi) atomicOr(&buf[d + 2], hi);
 }
 
-__global__ __launch_bounds__(kThreads) void png_encode_kernel(uint8_t* out, int64_t out_capacity, int32_t* seg_bytes, uint32_t* seg_adler,
-                                                              const uint8_t* src, int64_t src_bytes, int H, int W, int C) {
-  __shared__ uint32_t rawd[kRawDwords];            // the raw rows; later the bit buffer
-  __shared__ __align__(4) uint8_t filt[kMaxSeg + 4];
+// The compress stage both encoders share: the n <= kMaxSeg filtered bytes filt[] (LDS) -> one deflate block (+ the empty stored block of
+// a non-final segment) in `slot`, its byte count in *nbytes, its Adler parts in adler_out[0..1].  bits: LDS of (n + 16 + 3) / 4 dwords
+// that nobody reads any more (the bit buffer).  Called by the whole workgroup of kThreads behind a barrier that made filt[] visible.
+// Its tables are static LDS of its own: a kernel that calls it adds them to its filtered bytes and its bit buffer.
+__device__ __forceinline__ void compress_segment(uint32_t* bits, const uint8_t* filt, int n, bool final_seg, uint32_t* slot,
+                                                 int32_t* nbytes, uint32_t* adler_out) {
   __shared__ int scan[2][kThreads];
   __shared__ int hist[kLit + 2];
   __shared__ uint8_t lens[kLit + 2];
@@ -201,103 +205,14 @@ __global__ __launch_bounds__(kThreads) void png_encode_kernel(uint8_t* out, int6
   __shared__ Huff huff;
   __shared__ int sh_misc[8];                       // 0 matches, 1 nlit, 2 cl tokens, 3 header bits, 4 ncl
   __shared__ uint32_t sh_adler[2];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int seg = blockIdx.x, nseg = gridDim.x;
-  const int64_t img = blockIdx.y;
-  const int rb = C * W, L = rb + 1;
-  const int r0 = seg * kRows;
-  const int rows = min(kRows, H - r0);
-  const int n = rows * L;
-  const bool final_seg = seg == nseg - 1;
-
-  // ---- load: rows fr .. r0 + rows - 1 as one byte range
-  const int fr = max(r0 - 1, 0);
-  const int nload = (r0 + rows - fr) * rb;
-  const uintptr_t lo = (uintptr_t)src, hi = lo + (uintptr_t)src_bytes;
-  const uintptr_t A = lo + (uintptr_t)((img * H + fr) * rb);
-  const int mis = (int)(A & 3);
-  for (int d = tid; d * 4 < mis + nload; d += kThreads) {
-    const uintptr_t p = (A & ~(uintptr_t)3) + 4u * (uintptr_t)d;
-    uint32_t v = 0;
-    if (p >= lo && p + 4 <= hi) {
-      v = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (p + k >= lo && p + k < hi) v |= (uint32_t)(*reinterpret_cast<const uint8_t*>(p + k)) << (8 * k);
-    }
-    rawd[d] = v;
-  }
+  const int tid = threadIdx.x;
+  const int buf_dwords = (n + 16 + 3) / 4;
+  for (int d = tid; d < buf_dwords; d += kThreads) bits[d] = 0;
   for (int i = tid; i < kLit + 2; i += kThreads) hist[i] = 0;
   if (tid < kClSyms) cl_hist[tid] = 0;
   if (tid < 8) sh_misc[tid] = 0;
   if (tid < 2) sh_adler[tid] = 0;
   __syncthreads();
-
-  // ---- filter: one wave per row
-  const uint8_t* ls = reinterpret_cast<const uint8_t*>(rawd) + mis;
-  for (int row = wave; row < rows; row += kWaves) {
-    const int y = r0 + row;
-    const uint8_t* cur = ls + (y - fr) * rb;
-    const bool has_up = y > 0;
-    int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-    for (int x = lane; x < rb; x += 64) {
-      const int v = cur[x];
-      const int a = x >= C ? cur[x - C] : 0;
-      const int b = has_up ? cur[x - rb] : 0;
-      const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
-      const int p = a + b - c;
-      const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-      const int pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-      int r;
-      r = v; s0 += r < 128 ? r : 256 - r;
-      r = (v - a) & 255; s1 += r < 128 ? r : 256 - r;
-      r = (v - b) & 255; s2 += r < 128 ? r : 256 - r;
-      r = (v - ((a + b) >> 1)) & 255; s3 += r < 128 ? r : 256 - r;
-      r = (v - pr) & 255; s4 += r < 128 ? r : 256 - r;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      s0 += __shfl_xor(s0, d, 64);
-      s1 += __shfl_xor(s1, d, 64);
-      s2 += __shfl_xor(s2, d, 64);
-      s3 += __shfl_xor(s3, d, 64);
-      s4 += __shfl_xor(s4, d, 64);
-    }
-    int type = 0, best = s0;
-    if (s1 < best) type = 1, best = s1;
-    if (s2 < best) type = 2, best = s2;
-    if (s3 < best) type = 3, best = s3;
-    if (s4 < best) type = 4, best = s4;
-    uint8_t* o = filt + row * L;
-    if (lane == 0) o[0] = (uint8_t)type;
-    for (int x = lane; x < rb; x += 64) {
-      const int v = cur[x];
-      const int a = x >= C ? cur[x - C] : 0;
-      const int b = has_up ? cur[x - rb] : 0;
-      const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
-      int pred = 0;
-      if (type == 1) {
-        pred = a;
-      } else if (type == 2) {
-        pred = b;
-      } else if (type == 3) {
-        pred = (a + b) >> 1;
-      } else if (type == 4) {
-        const int p = a + b - c;
-        const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
-        pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
-      }
-      o[1 + x] = (uint8_t)(v - pred);
-    }
-  }
-  __syncthreads();
-
-  // ---- the raw rows are done with: their LDS becomes the (zeroed) bit buffer
-  uint32_t* bits = rawd;
-  const int buf_dwords = (n + 16 + 3) / 4;
-  for (int d = tid; d < buf_dwords; d += kThreads) bits[d] = 0;
 
   // ---- chunks, stretch scans, Adler parts
   const int P = (n + kThreads - 1) / kThreads;
@@ -468,14 +383,269 @@ __global__ __launch_bounds__(kThreads) void png_encode_kernel(uint8_t* out, int6
   __syncthreads();
 
   // ---- store
-  uint32_t* slot = reinterpret_cast<uint32_t*>(out + img * out_capacity + (int64_t)seg * seg_bound(kRows, rb));
   for (int d = tid; d * 4 < total; d += kThreads) slot[d] = bits[d];
   if (tid == 0) {
-    const int64_t k = img * nseg + seg;
-    seg_bytes[k] = total;
-    seg_adler[2 * k] = sh_adler[0] % kAdler;
-    seg_adler[2 * k + 1] = sh_adler[1] % kAdler;
+    *nbytes = total;
+    adler_out[0] = sh_adler[0] % kAdler;
+    adler_out[1] = sh_adler[1] % kAdler;
   }
+}
+
+__global__ __launch_bounds__(kThreads) void png_encode_kernel(uint8_t* out, int64_t out_capacity, int32_t* seg_bytes, uint32_t* seg_adler,
+                                                              const uint8_t* src, int64_t src_bytes, int H, int W, int C) {
+  __shared__ uint32_t rawd[kRawDwords];            // the raw rows; later the bit buffer
+  __shared__ __align__(4) uint8_t filt[kMaxSeg + 4];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int seg = blockIdx.x, nseg = gridDim.x;
+  const int64_t img = blockIdx.y;
+  const int rb = C * W, L = rb + 1;
+  const int r0 = seg * kRows;
+  const int rows = min(kRows, H - r0);
+  const int n = rows * L;
+  const bool final_seg = seg == nseg - 1;
+
+  // ---- load: rows fr .. r0 + rows - 1 as one byte range
+  const int fr = max(r0 - 1, 0);
+  const int nload = (r0 + rows - fr) * rb;
+  const uintptr_t lo = (uintptr_t)src, hi = lo + (uintptr_t)src_bytes;
+  const uintptr_t A = lo + (uintptr_t)((img * H + fr) * rb);
+  const int mis = (int)(A & 3);
+  for (int d = tid; d * 4 < mis + nload; d += kThreads) {
+    const uintptr_t p = (A & ~(uintptr_t)3) + 4u * (uintptr_t)d;
+    uint32_t v = 0;
+    if (p >= lo && p + 4 <= hi) {
+      v = *reinterpret_cast<const uint32_t*>(p);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (p + k >= lo && p + k < hi) v |= (uint32_t)(*reinterpret_cast<const uint8_t*>(p + k)) << (8 * k);
+    }
+    rawd[d] = v;
+  }
+  __syncthreads();
+
+  // ---- filter: one wave per row
+  const uint8_t* ls = reinterpret_cast<const uint8_t*>(rawd) + mis;
+  for (int row = wave; row < rows; row += kWaves) {
+    const int y = r0 + row;
+    const uint8_t* cur = ls + (y - fr) * rb;
+    const bool has_up = y > 0;
+    int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    for (int x = lane; x < rb; x += 64) {
+      const int v = cur[x];
+      const int a = x >= C ? cur[x - C] : 0;
+      const int b = has_up ? cur[x - rb] : 0;
+      const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
+      const int p = a + b - c;
+      const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+      const int pr = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+      int r;
+      r = v; s0 += r < 128 ? r : 256 - r;
+      r = (v - a) & 255; s1 += r < 128 ? r : 256 - r;
+      r = (v - b) & 255; s2 += r < 128 ? r : 256 - r;
+      r = (v - ((a + b) >> 1)) & 255; s3 += r < 128 ? r : 256 - r;
+      r = (v - pr) & 255; s4 += r < 128 ? r : 256 - r;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+      s0 += __shfl_xor(s0, d, 64);
+      s1 += __shfl_xor(s1, d, 64);
+      s2 += __shfl_xor(s2, d, 64);
+      s3 += __shfl_xor(s3, d, 64);
+      s4 += __shfl_xor(s4, d, 64);
+    }
+    int type = 0, best = s0;
+    if (s1 < best) type = 1, best = s1;
+    if (s2 < best) type = 2, best = s2;
+    if (s3 < best) type = 3, best = s3;
+    if (s4 < best) type = 4, best = s4;
+    uint8_t* o = filt + row * L;
+    if (lane == 0) o[0] = (uint8_t)type;
+    for (int x = lane; x < rb; x += 64) {
+      const int v = cur[x];
+      const int a = x >= C ? cur[x - C] : 0;
+      const int b = has_up ? cur[x - rb] : 0;
+      const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
+      int pred = 0;
+      if (type == 1) {
+        pred = a;
+      } else if (type == 2) {
+        pred = b;
+      } else if (type == 3) {
+        pred = (a + b) >> 1;
+      } else if (type == 4) {
+        const int p = a + b - c;
+        const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+        pred = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+      }
+      o[1 + x] = (uint8_t)(v - pred);
+    }
+  }
+  __syncthreads();
+
+  // ---- the raw rows are done with: their LDS becomes the bit buffer
+  const int64_t k = img * nseg + seg;
+  compress_segment(rawd, filt, n, final_seg, reinterpret_cast<uint32_t*>(out + img * out_capacity + (int64_t)seg * seg_bound(kRows, rb)),
+                   seg_bytes + k, seg_adler + 2 * k);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ragged batches
+// Whole photos of any width, each with its own size inside one packed buffer: the filtered stream of an image is cut into segments of
+// kRagSeg BYTES (a boundary may fall anywhere), so the LDS need does not depend on the row length.
+//   png_row_filter_kernel      one workgroup per (image, row): the five sums straight from global memory -> the row's type byte
+//   png_ragged_encode_kernel   one workgroup per (image, segment): the segment's filtered bytes rebuilt into LDS, compress_segment
+//   png_compact_kernel         one workgroup per (image, segment): the slot -> its place in the image's contiguous payload
+constexpr int kRagSeg = VSP_PNG_RAGGED_SEG_BYTES;
+constexpr int kRagSlot = (kRagSeg + 10 + 3) / 4 * 4;
+constexpr int kRowThreads = 256, kCopyThreads = 256;
+static_assert(kRagSeg <= kMaxSeg && (kRagSeg + kThreads - 1) / kThreads <= 49, "compress_segment's chunks hold at most 49 bytes");
+static_assert(kRagSlot == VSP_PNG_RAGGED_SLOT_BYTES, "the header's slot size");
+
+__device__ __forceinline__ int paeth(int a, int b, int c) {
+  const int p = a + b - c;
+  const int pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+  return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+
+__device__ __forceinline__ int abs8(int r) { return r < 128 ? r : 256 - r; }
+
+// the last item whose `first` (seg0 or row0, ascending from 0) is <= j
+template <class F>
+__device__ __forceinline__ int find_image(int n, int j, F first) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (first(mid) <= j) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// segments of an image of h rows of L filtered bytes
+__host__ __device__ inline int rag_segments(int h, int L) { return (int)(((int64_t)h * L + kRagSeg - 1) / kRagSeg); }
+
+// grid (rows of the call), kRowThreads
+__global__ __launch_bounds__(kRowThreads) void png_row_filter_kernel(uint8_t* __restrict__ types, const uint8_t* __restrict__ src,
+                                                                     const vsp_png_item* __restrict__ items, int n, int C) {
+  __shared__ int part[kRowThreads / 64][5];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x;
+  const vsp_png_item it = items[find_image(n, j, [&](int i) { return items[i].row0; })];
+  const int y = j - it.row0;
+  if (y < 0 || y >= it.h) return;
+  const int rb = C * it.w;
+  const uint8_t* cur = src + it.src_off + (int64_t)y * rb;
+  const bool has_up = y > 0;
+  int s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+  for (int x = tid; x < rb; x += kRowThreads) {
+    const int v = cur[x];
+    const int a = x >= C ? cur[x - C] : 0;
+    const int b = has_up ? cur[x - rb] : 0;
+    const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
+    s0 += abs8(v);
+    s1 += abs8((v - a) & 255);
+    s2 += abs8((v - b) & 255);
+    s3 += abs8((v - ((a + b) >> 1)) & 255);
+    s4 += abs8((v - paeth(a, b, c)) & 255);
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    s0 += __shfl_xor(s0, d, 64);
+    s1 += __shfl_xor(s1, d, 64);
+    s2 += __shfl_xor(s2, d, 64);
+    s3 += __shfl_xor(s3, d, 64);
+    s4 += __shfl_xor(s4, d, 64);
+  }
+  if (lane == 0) part[wave][0] = s0, part[wave][1] = s1, part[wave][2] = s2, part[wave][3] = s3, part[wave][4] = s4;
+  __syncthreads();
+  if (tid == 0) {
+    int s[5];
+    for (int k = 0; k < 5; ++k) {
+      s[k] = 0;
+      for (int w = 0; w < kRowThreads / 64; ++w) s[k] += part[w][k];
+    }
+    int type = 0, best = s[0];
+    for (int k = 1; k < 5; ++k)
+      if (s[k] < best) type = k, best = s[k];
+    types[j] = (uint8_t)type;
+  }
+}
+
+// grid (segments of the call), kThreads
+__global__ __launch_bounds__(kThreads) void png_ragged_encode_kernel(uint8_t* __restrict__ slots, int32_t* __restrict__ seg_bytes,
+                                                                     uint32_t* __restrict__ seg_adler, const uint8_t* __restrict__ types,
+                                                                     const uint8_t* __restrict__ src, const vsp_png_item* __restrict__ items,
+                                                                     int n_images, int C) {
+  __shared__ uint32_t bits[(kRagSeg + 16 + 3) / 4];
+  __shared__ __align__(4) uint8_t filt[kRagSeg + 4];
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x;
+  const vsp_png_item it = items[find_image(n_images, j, [&](int i) { return items[i].seg0; })];
+  const int rb = C * it.w, L = rb + 1;
+  const int li = j - it.seg0, nseg = rag_segments(it.h, L);
+  if (li < 0 || li >= nseg) return;                 // cannot happen with a table the host has checked
+  const int64_t total = (int64_t)it.h * L, p0 = (int64_t)li * kRagSeg;
+  const int n = (int)min((int64_t)kRagSeg, total - p0);
+  const int row0 = (int)(p0 / L), col0 = (int)(p0 - (int64_t)row0 * L);
+  const uint8_t* img = src + it.src_off;
+  const uint8_t* trow = types + it.row0;
+  for (int i = tid; i < n; i += kThreads) {
+    const uint32_t t = (uint32_t)(col0 + i);        // below kRagSeg + L
+    const uint32_t dr = t / (uint32_t)L;
+    const int col = (int)(t - dr * (uint32_t)L), y = row0 + (int)dr;
+    const int type = trow[y];
+    int r = type;
+    if (col > 0) {
+      const int x = col - 1;
+      const uint8_t* cur = img + (int64_t)y * rb;
+      const bool has_up = y > 0;
+      const int v = cur[x];
+      const int a = x >= C ? cur[x - C] : 0;
+      const int b = has_up ? cur[x - rb] : 0;
+      const int c = (has_up && x >= C) ? cur[x - rb - C] : 0;
+      const int pred = type == 1 ? a : type == 2 ? b : type == 3 ? (a + b) >> 1 : type == 4 ? paeth(a, b, c) : 0;
+      r = v - pred;
+    }
+    filt[i] = (uint8_t)r;
+  }
+  __syncthreads();
+  compress_segment(bits, filt, n, li == nseg - 1, reinterpret_cast<uint32_t*>(slots + (int64_t)j * kRagSlot), seg_bytes + j,
+                   seg_adler + 2 * (int64_t)j);
+}
+
+// grid (segments of the call), kCopyThreads
+__global__ __launch_bounds__(kCopyThreads) void png_compact_kernel(uint8_t* __restrict__ out, int32_t* __restrict__ idat_bytes,
+                                                                   const uint8_t* __restrict__ slots, const int32_t* __restrict__ seg_bytes,
+                                                                   const vsp_png_item* __restrict__ items, int n_images, int C) {
+  __shared__ long long wsum[kCopyThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = blockIdx.x;
+  const int im = find_image(n_images, j, [&](int i) { return items[i].seg0; });
+  const vsp_png_item it = items[im];
+  const int L = C * it.w + 1;
+  const int li = j - it.seg0, nseg = rag_segments(it.h, L);
+  if (li < 0 || li >= nseg) return;
+  long long sum = 0;                                 // an image's payload can pass 2^31 by its 10 bytes per segment
+  for (int k = tid; k < li; k += kCopyThreads) sum += min(max(seg_bytes[it.seg0 + k], 0), kRagSlot);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+  if (lane == 0) wsum[wave] = sum;
+  __syncthreads();
+  int64_t off = 0;
+  for (int w = 0; w < kCopyThreads / 64; ++w) off += wsum[w];
+  const int nb = min(max(seg_bytes[j], 0), kRagSlot);
+  const int64_t bound = (int64_t)it.h * L + 10 * (int64_t)nseg;
+  if (off + nb > bound) return;                      // cannot happen: every segment stays within its stored form
+  const uint8_t* s = slots + (int64_t)j * kRagSlot;
+  uint8_t* d = out + it.out_off + off;
+  for (int i = tid; i < nb; i += kCopyThreads) d[i] = s[i];
+  if (li == nseg - 1 && tid == 0) idat_bytes[im] = (int32_t)(off + nb);
+}
+
+constexpr size_t k2GiB = (size_t)1 << 31;
+
+bool rag_size_ok(int H, int W, int C) {
+  return H > 0 && W > 0 && (C == 1 || C == 3) && (int64_t)W * C <= VSP_PNG_RAGGED_MAX_ROW_BYTES && (uint64_t)H * W * C < k2GiB;
 }
 
 }  // namespace
@@ -510,6 +680,75 @@ int vsp_png_encode_u8(uint8_t* out, size_t out_capacity, int32_t* seg_bytes, uin
   png_encode_kernel<<<dim3((unsigned)nseg, (unsigned)B), kThreads, 0, vsp::as_stream(stream)>>>(
       out, (int64_t)out_capacity, seg_bytes, seg_adler, src, (int64_t)B * H * W * C, H, W, C);
   return vsp::check_launch("png_encode");
+}
+
+int vsp_png_ragged_segments(int H, int W, int C) {
+  if (!rag_size_ok(H, W, C)) return 0;
+  return rag_segments(H, W * C + 1);
+}
+
+size_t vsp_png_ragged_image_bound(int H, int W, int C) {
+  if (!rag_size_ok(H, W, C)) return 0;
+  return (size_t)H * ((size_t)W * C + 1) + 10 * (size_t)rag_segments(H, W * C + 1);
+}
+
+size_t vsp_png_ragged_work_bytes(int64_t segments, int64_t rows) {
+  if (segments < 0 || rows < 0) return 0;
+  return (size_t)segments * (VSP_PNG_RAGGED_SLOT_BYTES + 4) + ((size_t)rows + 3) / 4 * 4;
+}
+
+int vsp_png_encode_ragged_u8(uint8_t* out, size_t out_bytes, int32_t* idat_bytes, uint32_t* seg_adler, uint8_t* work, size_t work_bytes,
+                             const uint8_t* src, size_t src_bytes, const vsp_png_item* items, const vsp_png_item* items_dev, int n, int C,
+                             vsp_stream_t stream) {
+  VSP_REQUIRE(n >= 0, "png_encode_ragged: %d images", n);
+  VSP_REQUIRE(C == 1 || C == 3, "png_encode_ragged: %d channels (1 or 3)", C);
+  if (n > VSP_PNG_RAGGED_MAX_IMAGES) return vsp::fail(VSP_ENOTSUP, "png_encode_ragged: %d images (max %d)", n, VSP_PNG_RAGGED_MAX_IMAGES);
+  if (n == 0) return VSP_OK;
+  VSP_REQUIRE(out && idat_bytes && seg_adler && work && src && items && items_dev, "png_encode_ragged: null pointer");
+  VSP_REQUIRE((reinterpret_cast<uintptr_t>(work) & 3u) == 0 && (reinterpret_cast<uintptr_t>(idat_bytes) & 3u) == 0 &&
+                  (reinterpret_cast<uintptr_t>(seg_adler) & 3u) == 0,
+              "png_encode_ragged: work, idat_bytes and seg_adler must be 4-byte aligned");
+  if (src_bytes >= k2GiB || out_bytes >= k2GiB || work_bytes >= k2GiB)
+    return vsp::fail(VSP_ENOTSUP, "png_encode_ragged: a buffer of 2 GiB or more (src %zu, out %zu, work %zu)", src_bytes, out_bytes, work_bytes);
+  int64_t segs = 0, rows = 0, src_end = 0, out_end = 0;
+  for (int i = 0; i < n; ++i) {
+    const vsp_png_item& it = items[i];
+    VSP_REQUIRE(it.h > 0 && it.w > 0, "png_encode_ragged: image %d is %d x %d", i, it.h, it.w);
+    if ((int64_t)it.w * C > VSP_PNG_RAGGED_MAX_ROW_BYTES)
+      return vsp::fail(VSP_ENOTSUP, "png_encode_ragged: image %d has rows of %lld bytes (max %d)", i, (long long)it.w * C,
+                       VSP_PNG_RAGGED_MAX_ROW_BYTES);
+    const uint64_t bytes = (uint64_t)it.h * it.w * C;
+    VSP_REQUIRE(it.src_off >= src_end && (uint64_t)it.src_off + bytes <= src_bytes,
+                "png_encode_ragged: image %d (offset %lld, %llu bytes) overlaps the image before it or leaves src (%zu bytes)", i,
+                (long long)it.src_off, (unsigned long long)bytes, src_bytes);
+    src_end = it.src_off + (int64_t)bytes;
+    const int L = it.w * C + 1, nseg = rag_segments(it.h, L);
+    const uint64_t bound = (uint64_t)it.h * L + 10 * (uint64_t)nseg;
+    VSP_REQUIRE(it.out_off >= out_end && (uint64_t)it.out_off + bound <= out_bytes,
+                "png_encode_ragged: the output range of image %d (offset %lld, %llu bytes) overlaps the one before it or leaves out (%zu bytes)",
+                i, (long long)it.out_off, (unsigned long long)bound, out_bytes);
+    out_end = it.out_off + (int64_t)bound;
+    VSP_REQUIRE(it.seg0 == segs && it.row0 == rows, "png_encode_ragged: image %d has seg0 %d and row0 %d, expected %lld and %lld", i, it.seg0,
+                it.row0, (long long)segs, (long long)rows);
+    segs += nseg;
+    rows += it.h;
+    if (segs > VSP_PNG_RAGGED_MAX_SEGMENTS)
+      return vsp::fail(VSP_ENOTSUP, "png_encode_ragged: more than %d segments in one call", VSP_PNG_RAGGED_MAX_SEGMENTS);
+  }
+  VSP_REQUIRE(vsp_png_ragged_work_bytes(segs, rows) <= work_bytes, "png_encode_ragged: work of %zu bytes, %lld segments and %lld rows need %zu",
+              work_bytes, (long long)segs, (long long)rows, vsp_png_ragged_work_bytes(segs, rows));
+  uint8_t* slots = work;
+  int32_t* seg_bytes = reinterpret_cast<int32_t*>(work + (size_t)segs * VSP_PNG_RAGGED_SLOT_BYTES);
+  uint8_t* types = work + (size_t)segs * (VSP_PNG_RAGGED_SLOT_BYTES + 4);
+  hipStream_t s = vsp::as_stream(stream);
+  png_row_filter_kernel<<<(unsigned)rows, kRowThreads, 0, s>>>(types, src, items_dev, n, C);
+  int rc = vsp::check_launch("png_row_filter");
+  if (rc != VSP_OK) return rc;
+  png_ragged_encode_kernel<<<(unsigned)segs, kThreads, 0, s>>>(slots, seg_bytes, seg_adler, types, src, items_dev, n, C);
+  rc = vsp::check_launch("png_ragged_encode");
+  if (rc != VSP_OK) return rc;
+  png_compact_kernel<<<(unsigned)segs, kCopyThreads, 0, s>>>(out, idat_bytes, slots, seg_bytes, items_dev, n, C);
+  return vsp::check_launch("png_compact");
 }
 
 }  // extern "C"

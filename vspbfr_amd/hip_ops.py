@@ -1742,6 +1742,81 @@ def png_encode(u8, guard=0):
     return out, seg_bytes, seg_adler, slot
 
 
+PNG_RAGGED_SEG_BYTES = 24576                  # include/vspbfr_hip.h VSP_PNG_RAGGED_SEG_BYTES
+PNG_RAGGED_SLOT_BYTES = 24588                 # VSP_PNG_RAGGED_SLOT_BYTES
+PNG_RAGGED_MAX_ROW_BYTES = 1 << 20            # VSP_PNG_RAGGED_MAX_ROW_BYTES
+PNG_RAGGED_MAX_IMAGES = 4096
+PNG_RAGGED_MAX_SEGMENTS = 65535
+PNG_LIMIT_BYTES = 1 << 31                     # a buffer of this size or more: VSP_ENOTSUP
+
+
+def png_ragged_layout(sizes, offsets=None, C=3):
+    """What one vsp_png_encode_ragged_u8 call over packed (h, w, C) images of `sizes` = [(h, w), ...] at the byte `offsets` of the source
+    buffer (default: back to back) needs: (rows, out_bytes, work_bytes, segments) -- per image the vsp_png_item fields (src_off, out_off,
+    h, w, seg0, row0) with the payloads at 16-byte boundaries of `out`.  None when a size helper refuses a size.  The one place the Python
+    side works this out: png_encode_ragged and png.ragged_serves both ask here."""
+    rows, src, out, segs, nrows = [], 0, 0, 0, 0
+    for i, (h, w) in enumerate(sizes):
+        h, w = int(h), int(w)
+        nseg = lib.vsp_png_ragged_segments(h, w, C)
+        if nseg == 0:
+            return None
+        off = src if offsets is None else int(offsets[i])
+        rows.append((off, out, h, w, segs, nrows))
+        src, out = off + C * h * w, out + (lib.vsp_png_ragged_image_bound(h, w, C) + 15) // 16 * 16
+        segs, nrows = segs + nseg, nrows + h
+    return rows, out, lib.vsp_png_ragged_work_bytes(segs, nrows), segs
+
+
+def png_encode_ragged(buffer, sizes, offsets=None, C=3, guard=0):
+    """Row filters + deflate of packed (h, w, C) uint8 images of any width on the current stream (vsp_png_encode_ragged_u8,
+    csrc/png.hip).  buffer: 1-D uint8 device tensor; image i lies at byte offsets[i] (default: back to back), any alignment.  Returns
+    (out uint8, idat_bytes (n,) int32, seg_adler (segments, 2) int32 bit patterns of uint32, out_offsets, work, layout): image i's zlib
+    payload is out[out_offsets[i] : out_offsets[i] + idat_bytes[i]]; vspbfr_amd.png.assemble_ragged frames it.  work holds the slots, the
+    segment sizes and the filter types as the header lays them out (tests read them); layout = (rows, out_bytes, work_bytes, segments).
+    guard: every payload's range is lengthened by this many bytes the kernels must leave alone, and `out` is pre-filled with 0xA5
+    (tests).  Nothing is synchronised: the item table goes up from pinned memory on the current stream.  Wrong arguments raise
+    RuntimeError (the entry's message); a call above the header's limits raises NotImplementedError."""
+    import ctypes as Ct
+    from ._lib import PngItem
+    _u8(buffer, "buffer")
+    n = len(sizes)
+    if buffer.dim() != 1 or (offsets is not None and len(offsets) != n):
+        raise RuntimeError("png_encode_ragged: a flat buffer, and one offset per size")
+    dev = buffer.device
+    if n == 0:
+        return (torch.empty(0, device=dev, dtype=torch.uint8), torch.empty(0, device=dev, dtype=torch.int32),
+                torch.empty((0, 2), device=dev, dtype=torch.int32), [], torch.empty(0, device=dev, dtype=torch.uint8), ([], 0, 0, 0))
+    if any(int(h) < 1 or int(w) < 1 for h, w in sizes) or C not in (1, 3):
+        raise RuntimeError(f"png_encode_ragged: sizes {list(sizes)}, {C} channels")
+    layout = png_ragged_layout(sizes, offsets, C)
+    if layout is None:
+        raise NotImplementedError(f"png_encode_ragged: sizes {list(sizes)} above the limits of vsp_png_encode_ragged_u8")
+    rows, out_bytes, work_bytes, segs = layout
+    if guard:
+        rows = [(r[0], r[1] + i * guard) + r[2:] for i, r in enumerate(rows)]
+        out_bytes += n * guard
+        layout = (rows, out_bytes, work_bytes, segs)
+    if max(buffer.numel(), out_bytes, work_bytes) >= PNG_LIMIT_BYTES or n > PNG_RAGGED_MAX_IMAGES or segs > PNG_RAGGED_MAX_SEGMENTS:
+        raise NotImplementedError(f"png_encode_ragged: {n} images, {segs} segments, buffers of {buffer.numel()}, {out_bytes} and {work_bytes} "
+                                  "bytes reach the limits of vsp_png_encode_ragged_u8")
+    table = torch.empty(n * Ct.sizeof(PngItem), dtype=torch.uint8, pin_memory=True)
+    items = (PngItem * n).from_address(table.data_ptr())
+    for i, row in enumerate(rows):
+        items[i] = PngItem(*row)
+    out = torch.full((out_bytes,), 0xA5, device=dev, dtype=torch.uint8) if guard else torch.empty(out_bytes, device=dev, dtype=torch.uint8)
+    work = torch.empty(work_bytes, device=dev, dtype=torch.uint8)
+    idat = torch.empty(n, device=dev, dtype=torch.int32)
+    seg_adler = torch.empty((segs, 2), device=dev, dtype=torch.int32)
+    items_dev = table.to(dev, non_blocking=True)
+    rc = lib.vsp_png_encode_ragged_u8(_ptr(out), out_bytes, _ptr(idat), _ptr(seg_adler), _ptr(work), work_bytes, _ptr(buffer), buffer.numel(),
+                                      Ct.c_void_p(table.data_ptr()), _ptr(items_dev), n, C, _stream())
+    if rc == -3:
+        raise NotImplementedError(_lib.last_error())
+    check(rc, "png_encode_ragged")
+    return out, idat, seg_adler, [r[1] for r in rows], work, layout
+
+
 JPEG_SUBSAMPLING = {"444": 0, "420": 2}      # include/vspbfr_hip.h VSP_JPEG_444 / VSP_JPEG_420 (Pillow's numbers)
 JPEG_LIMIT_BYTES = 1 << 31                    # a buffer of this size or more: VSP_ENOTSUP
 

@@ -15,6 +15,8 @@ where the decoder wrote them; PNG files keep Pillow's decode.
 
 `PngWriter(encode="device")` is the opt-in device encoder of the other end (`restoration_metrics --encode device`): row filters and deflate run
 on the device (vspbfr_amd.png, vsp_png_encode_u8) and the worker threads only frame and write the files; the pixels are those of the host path.
+`PngWriter.submit_photos` writes a group of whole photos from their packed buffer; with encode="device" one call of the ragged entry
+(vsp_png_encode_ragged_u8, any width) codes them all (`restore_photos --png_encode device`).
 
 `JpegWriter` writes uint8 RGB images as baseline JPEG files (`restore_photos --format jpg`): encode="device" codes them on the device
 (vspbfr_amd.jpeg, vsp_jpeg_encode_u8), encode="host" hands them to Pillow at the same parameters; the two routes write equal bytes."""
@@ -235,6 +237,28 @@ class PngWriter:
         ev.record()
         self.pending.append(self.pool.submit(self._encode, host, ev, list(paths)))
         return u8
+
+    def submit_photos(self, buffer, sizes, offsets, paths):
+        """buffer: flat uint8 device tensor holding (h, w, 3) photos of `sizes` = [(h, w), ...] at the byte `offsets` (ascending, as
+        photo.FacePlan.out_off lays them out), one path per photo.  encode="device": ONE ragged call codes the whole group
+        (vspbfr_amd.png.enqueue_ragged, vsp_png_encode_ragged_u8) and a worker frames and writes the files; otherwise, and for a group the
+        entry does not take, every photo takes the pinned copy + PIL route of submit()."""
+        sizes, offsets, paths = [(int(h), int(w)) for h, w in sizes], [int(o) for o in offsets], list(paths)
+        if not len(sizes) == len(offsets) == len(paths):
+            raise ValueError("PngWriter.submit_photos: one size, offset and path per photo")
+        if self.encode == "device" and sizes:
+            from . import png
+            if png.ragged_serves(sizes, 3):
+                job = png.enqueue_ragged(buffer, sizes, offsets)
+                self.pending.append(self.pool.submit(self._write, job, paths))
+                return
+        for (h, w), o, p in zip(sizes, offsets, paths):
+            u8 = buffer[o:o + 3 * h * w].view(1, h, w, 3)
+            host = torch.empty(u8.shape, dtype=torch.uint8, pin_memory=True)
+            host.copy_(u8, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self.pending.append(self.pool.submit(self._encode, host, ev, [p]))
 
     @staticmethod
     def _encode(host, ev, paths):

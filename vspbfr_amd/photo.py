@@ -478,7 +478,8 @@ class PhotoRestorer:
         """photos: uint8 (h, w, 3) arrays -- or their (h, w) with device_photos, the packed device buffer that holds them back to back
         (jpeg.decode_files) --; landmarks: per photo a list of (5, 2) point sets (None or [] for none) ->
         (output photos: device uint8 (upscale h, upscale w, 3) tensors, crops (F, S, S, 3) uint8, restored (F, S, S, 3) uint8, plan);
-        with a colour fix a fifth element, the fixed crops (F, S, S, 3) uint8 that were pasted (`restored` stays the network's output)"""
+        with a colour fix a fifth element, the fixed crops (F, S, S, 3) uint8 that were pasted (`restored` stays the network's output).
+        plan.out_packed is the packed buffer the output photos are views of (photo k at byte plan.out_off[k], plan.out_shape[k])"""
         import torch
 
         from . import hip_ops
@@ -487,7 +488,8 @@ class PhotoRestorer:
         S = self.size
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)
-            head = (plan.split(plan.background(device)), empty, empty, plan)
+            plan.out_packed = plan.background(device)
+            head = (plan.split(plan.out_packed), empty, empty, plan)
             return head if self.color_fix is None else head + (empty,)
         crops, low = crop_faces(plan, device, u8=True, f32=True, border=self.border)
         restored = []
@@ -497,8 +499,8 @@ class PhotoRestorer:
                 restored.append(hip_ops.quantize_u8_nhwc(out["restored"].contiguous(), -1.0, 1.0))
         restored = torch.cat(restored) if len(restored) > 1 else restored[0]
         if self.color_fix is None:
-            out = paste_faces(plan, restored, device, self.ramp)
+            out = plan.out_packed = paste_faces(plan, restored, device, self.ramp)
             return plan.split(out), crops, restored, plan
         fixed = color_fix(crops, restored, self.color_fix, plan, device, self.color_levels)
-        out = paste_faces(plan, fixed, device, self.ramp)
+        out = plan.out_packed = paste_faces(plan, fixed, device, self.ramp)
         return plan.split(out), crops, restored, plan, fixed

@@ -6,7 +6,16 @@ PNG chunks with `zlib.crc32` -- which is not the hot path: the bytes are on the 
     enqueue(u8) -> Job              the asynchronous form imageio.PngWriter uses: job.files() waits for the job's event
     assemble(...)                   the host framing alone
 
-A shape above the kernel's limits is encoded by PIL, so a caller always gets valid files."""
+A shape above the kernel's limits is encoded by PIL, so a caller always gets valid files.
+
+Whole photos -- any width, each its own size inside one packed buffer, as photo.FacePlan holds them -- take the ragged entry
+(vsp_png_encode_ragged_u8), which cuts an image's filtered stream into segments of RAGGED_SEG_BYTES bytes instead of rows:
+
+    encode_ragged(buffer, sizes, offsets) -> [bytes]     packed (h, w, C) images of different sizes
+    enqueue_ragged(buffer, sizes, offsets) -> RaggedJob  the asynchronous form imageio.PngWriter.submit_photos uses
+    ragged_serves(sizes, C)                              whether one call of the entry takes these images
+
+Its files differ in bytes from encode_batch's for the same pixels (the segmentation differs); both are valid PNGs of those pixels."""
 import io
 import zlib
 
@@ -78,6 +87,117 @@ class Job:
 def enqueue(u8):
     """encoder + asynchronous device-to-host copies on the current stream; no host synchronisation"""
     return Job(u8)
+
+
+RAGGED_SEG_BYTES = 24576      # VSP_PNG_RAGGED_SEG_BYTES
+
+
+def _sizes(sizes):
+    return [(int(h), int(w)) for h, w in sizes]
+
+
+def ragged_serves(sizes, C=3):
+    """True when one vsp_png_encode_ragged_u8 call takes packed (h, w, C) images of these sizes: C 1 or 3, rows of at most 2^20 bytes,
+    every buffer below 2 GiB, the image and segment counts within the header's caps"""
+    from . import hip_ops
+    sizes = _sizes(sizes)
+    if C not in (1, 3) or not 1 <= len(sizes) <= hip_ops.PNG_RAGGED_MAX_IMAGES or any(h < 1 or w < 1 for h, w in sizes):
+        return False
+    layout = hip_ops.png_ragged_layout(sizes, None, C)
+    if layout is None or layout[3] > hip_ops.PNG_RAGGED_MAX_SEGMENTS:
+        return False
+    return max(sum(C * h * w for h, w in sizes), layout[1], layout[2]) < hip_ops.PNG_LIMIT_BYTES
+
+
+def assemble_ragged(payload, seg_adler, h, w, C):
+    """One image's file around its zlib payload (the segments back to back, as the compact kernel leaves them): seg_adler (nseg, 2) as
+    the kernel wrote them, segment k covering bytes k * RAGGED_SEG_BYTES .. of the h (1 + C w) filtered bytes"""
+    n = h * (1 + C * w)
+    a, b = 1, 0
+    for k in range((n + RAGGED_SEG_BYTES - 1) // RAGGED_SEG_BYTES):
+        nk = min(RAGGED_SEG_BYTES, n - k * RAGGED_SEG_BYTES)
+        b = (b + nk * a + (int(seg_adler[k][1]) & 0xFFFFFFFF)) % _ADLER
+        a = (a + (int(seg_adler[k][0]) & 0xFFFFFFFF)) % _ADLER
+    ihdr = w.to_bytes(4, "big") + h.to_bytes(4, "big") + bytes([8, 2 if C == 3 else 0, 0, 0, 0])
+    stream = b"\x78\x01" + bytes(payload) + (b << 16 | a).to_bytes(4, "big")
+    return _SIGNATURE + _chunk(b"IHDR", ihdr) + _chunk(b"IDAT", stream) + _chunk(b"IEND", b"")
+
+
+_side = {}
+
+
+def _side_stream(device):
+    """the stream of the payload copies: a worker thread's copy must not queue behind the next batch on the compute stream"""
+    key = torch.device(device).index
+    if key not in _side:
+        _side[key] = torch.cuda.Stream(device=device)
+    return _side[key]
+
+
+class RaggedJob:
+    """One ragged call in flight: the payloads on the device, their byte counts and the Adler parts on the way to pinned memory and the
+    event behind them.  files() waits for the event, copies only the used bytes of every payload and frames the files."""
+
+    def __init__(self, buffer, sizes, offsets=None, C=3):
+        from . import hip_ops
+        self.sizes, self.C = _sizes(sizes), C
+        self.out, idat, seg_adler, self.offsets, _, layout = hip_ops.png_encode_ragged(buffer, self.sizes, offsets, C)
+        self.seg0 = [r[4] for r in layout[0]] + [layout[3]]
+        self.idat = torch.empty(idat.shape, dtype=torch.int32, pin_memory=True)
+        self.idat.copy_(idat, non_blocking=True)
+        self.adler = torch.empty(seg_adler.shape, dtype=torch.int32, pin_memory=True)
+        self.adler.copy_(seg_adler, non_blocking=True)
+        self.event = torch.cuda.Event()
+        self.event.record()
+
+    def files(self):
+        self.event.synchronize()
+        totals = [int(v) for v in self.idat.numpy()]
+        host = torch.empty(max(sum(totals), 1), dtype=torch.uint8, pin_memory=True)
+        side = _side_stream(self.out.device)
+        with torch.cuda.stream(side):
+            at = 0
+            for off, nb in zip(self.offsets, totals):
+                host[at:at + nb].copy_(self.out[off:off + nb], non_blocking=True)
+                at += nb
+            side.synchronize()
+        data, adler, files, at = host.numpy(), self.adler.numpy(), [], 0
+        for i, ((h, w), nb) in enumerate(zip(self.sizes, totals)):
+            files.append(assemble_ragged(data[at:at + nb].tobytes(), adler[self.seg0[i]:self.seg0[i + 1]], h, w, self.C))
+            at += nb
+        self.out = None
+        return files
+
+
+def enqueue_ragged(buffer, sizes, offsets=None, C=3):
+    """the three kernels + the asynchronous copies of the byte counts and Adler parts on the current stream; no host synchronisation"""
+    return RaggedJob(buffer, sizes, offsets, C)
+
+
+def encode_ragged(buffer, sizes, offsets=None, C=3):
+    """flat uint8 device tensor holding (h, w, C) images of `sizes` = [(h, w), ...] at the byte `offsets` (default: back to back) -> the
+    files; PIL encodes a call the entry does not take"""
+    sizes = _sizes(sizes)
+    if not isinstance(buffer, torch.Tensor) or buffer.dtype != torch.uint8 or buffer.dim() != 1 or not buffer.is_contiguous():
+        raise RuntimeError("png.encode_ragged: a flat contiguous uint8 tensor")
+    if C not in (1, 3) or any(h < 1 or w < 1 for h, w in sizes):
+        raise RuntimeError(f"png.encode_ragged: sizes {sizes}, {C} channels")
+    if offsets is None:
+        offsets = [0] * len(sizes)
+        for i in range(1, len(sizes)):
+            offsets[i] = offsets[i - 1] + C * sizes[i - 1][0] * sizes[i - 1][1]
+    offsets = [int(o) for o in offsets]
+    if len(offsets) != len(sizes) or any(o < 0 or o + C * h * w > buffer.numel() for o, (h, w) in zip(offsets, sizes)):
+        raise RuntimeError(f"png.encode_ragged: {buffer.numel()} bytes for the sizes {sizes} at {offsets}")
+    if not sizes:
+        return []
+    if ragged_serves(sizes, C):
+        try:
+            return RaggedJob(buffer, sizes, offsets, C).files()
+        except NotImplementedError:
+            pass
+    arr = buffer.cpu().numpy()
+    return [_pil_file(arr[o:o + C * h * w].reshape(h, w, C)) for o, (h, w) in zip(offsets, sizes)]
 
 
 def _pil_file(arr):

@@ -2,7 +2,8 @@
 
     python -m vspbfr_amd.restore_photos --photos DIR --landmarks FILE.json --out DIR [--upscale {1,2,4}] [--save_faces]
         [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L]
-        [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] [--decode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] [--decode {host,device}]
+        [--png_encode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  There is no
@@ -38,6 +39,12 @@ files and lists `format`, `quality` and `subsampling`.  Default png: nothing cha
 csrc/jpeg_decode.hip) into the buffer the crop kernel reads; a PNG, a progressive or otherwise refused JPEG and a file whose
 scan the kernels flag take Pillow's decode inside the same group.  Equal output bytes either way.  With the flag (host or device)
 report.json lists `decode` per photo.  Default: Pillow, nothing changes.
+
+--png_encode device: the PNG files are coded on the device.  A group's output photos go through one call of the ragged encoder on the
+packed buffer they lie in (imageio.PngWriter.submit_photos, vsp_png_encode_ragged_u8, DESIGN 21: any width, every photo its own size),
+the --save_faces files through the uniform encoder (vsp_png_encode_u8).  The files hold the pixels of the host route; their bytes differ
+from Pillow's, as any two PNG encoders' do.  report.json then lists `png_encode`.  With --format jpg the flag needs --save_faces (no
+other file is a PNG).  Default host: Pillow, nothing changes.
 
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
@@ -106,10 +113,12 @@ def list_photos(root):
 def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
     lo, hi = shard_range(len(names), rank, world)
     os.makedirs(args.out, exist_ok=True)
-    writer = PngWriter()
+    png_device = getattr(args, "png_encode", None) == "device"
+    writer = PngWriter(encode="device") if png_device else PngWriter()
     jpg = getattr(args, "format", "png") == "jpg"
     photo_writer = JpegWriter(quality=args.quality, subsampling=args.subsampling, encode=args.encode) if jpg else writer
     ext = ".jpg" if jpg else ".png"
+    ragged = png_device and not jpg          # a group's photos go through one call of the ragged PNG encoder
     report = []
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
     for group in _groups(names[lo:hi], landmarks, args.batch):
@@ -121,10 +130,15 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
         else:
             photos, how = [_decode(os.path.join(args.photos, n)) for n in group], ["host"] * len(group)
             outs, crops, restored, plan, *fixed = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
-        for k, n in enumerate(group):
-            stem = os.path.join(args.out, os.path.splitext(n)[0])
+        stems = [os.path.join(args.out, os.path.splitext(n)[0]) for n in group]
+        for stem in stems:
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
-            photo_writer.submit(outs[k][None], [stem + ext])
+        if ragged:
+            writer.submit_photos(plan.out_packed, plan.out_shape, plan.out_off, [stem + ext for stem in stems])
+        for k, n in enumerate(group):
+            stem = stems[k]
+            if not ragged:
+                photo_writer.submit(outs[k][None], [stem + ext])
             mine = [i for i, kk in enumerate(plan.face_photo) if kk == k]
             if args.save_faces:
                 for j, i in enumerate(mine):
@@ -147,6 +161,8 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1):
         head.update(color_fix=restorer.color_fix, color_levels=restorer.color_levels)
     if jpg:
         head.update(format="jpg", quality=args.quality, subsampling=args.subsampling)
+    if getattr(args, "png_encode", None) is not None:
+        head.update(png_encode=args.png_encode)
     with open(os.path.join(args.out, name), "w") as f:
         json.dump(dict(head, photos=report), f, indent=1)
     return report
@@ -186,6 +202,8 @@ def main(argv=None):
                     help="--format jpg: code the file on the device (default) or with Pillow on the host; equal bytes")
     ap.add_argument("--decode", choices=["host", "device"], default=None,
                     help="decode baseline JPEG inputs on the device or everything with Pillow on the host (the default); equal bytes")
+    ap.add_argument("--png_encode", choices=["host", "device"], default=None,
+                    help="code the PNG files with Pillow on the host (the default) or on the device; equal pixels")
     args = ap.parse_args(argv)
     try:                       # the flags are checked before any model is loaded
         color_fix, color_levels = check_color_fix(args.color_fix, args.color_levels)
@@ -196,6 +214,8 @@ def main(argv=None):
             args.quality, args.subsampling, _ = check_params(DEFAULT_QUALITY if args.quality is None else args.quality,
                                                               args.subsampling or "420", DEFAULT_RESTART)
             args.encode = args.encode or "device"
+        if args.png_encode == "device" and args.format == "jpg" and not args.save_faces:
+            raise ValueError("--png_encode device with --format jpg needs --save_faces: no other file is a PNG")
     except ValueError as e:
         ap.error(str(e))
     if args.batch < 1 or args.inset < 0 or args.feather < 0:
