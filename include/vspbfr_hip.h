@@ -1145,6 +1145,75 @@ int vsp_jpeg_decode_u8(uint8_t* out, size_t out_bytes, int32_t* status, int32_t*
                        size_t in_bytes, const vsp_jpeg_dec_item* items, const vsp_jpeg_dec_item* items_dev, const uint8_t* tables,
                        const uint8_t* tables_dev, int n, int sub_bytes, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Face detection for whole photos: RetinaFace with the MobileNet-0.25 backbone in fp32 and its post-processing (csrc/detect.hip,
+ * vspbfr_amd/detect.py).  Activations are NCHW fp32; BatchNorm is folded into weight and bias on the host.  `act`: 0 = none,
+ * 1 = x < 0 ? slope x : x (slope 0 is ReLU).  tests/detect_ref.py restates the network in torch (float64 / float32) and the
+ * post-processing in NumPy.
+ *
+ *   entry      the first layer on the u8 photos: y (B, 8, ceil(Hc/2), ceil(Wc/2)) = act(conv3x3 stride 2 pad 1 of the canvas + b).  The
+ *              canvas (B, 3, Hc, Wc) is never stored: item i's (h, w, 3) RGB photo lies at the top-left of canvas `slot`, channel c of
+ *              the canvas is photo channel 2 - c minus mean (104, 117, 123)[c], and everything outside the photo is 0.  w is
+ *              [ci 3][tap 9][co 8].  A call writes the slots of its items in full and no other; items are given in host and device memory
+ *   sep        one depthwise-separable block: t = act(dw3x3 stride s pad 1 of x + bd), y = act(pw1x1 of t + bp), slope for both; t stays
+ *              in LDS.  wd is [Cin][9], wp [Cin][Cout].  Cin 1..256, Cout a multiple of 16 up to 256, stride 1 or 2,
+ *              OH = (H - 1) / s + 1
+ *   conv3x3    dense 3x3 stride 1 pad 1, w [Cin][9][Cout], Cin a multiple of 8, Cout 16, 32 or 64; y has y_ch channels and the result
+ *              goes to channels y_coff .. y_coff + Cout - 1 (the SSH concatenation)
+ *   lateral    y = act(conv1x1 of x + b) + up[b][co][floor(oy h2 / H)][floor(ox w2 / W)] (up may be null: no addition);
+ *              w [Cin][64], Cout = 64
+ *   heads      one level: 32 channels = conv1x1 of x (B, 64, H, W) with w [64][32] + b, channels 0..3 class, 4..11 box, 12..31
+ *              landmarks, written for cell p and anchor a as prior p0 + 2 p + a of conf (B, P, 2), loc (B, P, 4), lm (B, P, 10)
+ *   decode_nms per image, one workgroup: priors from the index -- level k = 0, 1, 2 has step 8, 16, 32, ceil(Hc / step)
+ *              x ceil(Wc / step) cells in raster order, two anchors of size (16, 32), (64, 128), (256, 512) per cell, centre
+ *              ((j + 0.5) step, (i + 0.5) step) --; score = 1 / (1 + exp(l0 - l1)); box centre c + loc[0:2] 0.1 m, size m exp(0.2
+ *              loc[2:4]); landmark k = c + lm[2k:2k+2] 0.1 m; all in canvas pixels.  Candidates: score > threshold with a finite box
+ *              and landmarks; the first max_candidates in the order (score descending, prior ascending) survive; greedy NMS in that
+ *              order, suppressed when IoU (plain areas) with a kept one > nms; the first max_faces kept ones are written to
+ *              faces[b * max_faces ..].  info[4 b ..] = faces written, status (VSP_DET_*), candidates before the cap, non-finite dropped.
+ *              No loop is bounded by data and none waits for another thread's write outside a barrier.
+ * VSP_EINVAL, nothing launched: a null pointer, a dimension outside the limits above, B < 0, an item outside `src` or a slot outside
+ * 0 .. B - 1, threshold outside [0, 1), nms outside [0, 1], max_candidates outside 1 .. VSP_DET_MAX_CANDIDATES, max_faces < 1, a `work`
+ * too small or not 16-byte aligned.  VSP_ENOTSUP: a tensor or buffer of 2 GiB or more.  B = 0 (n = 0) returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_DET_MAX_CANDIDATES 2048
+#define VSP_DET_MAX_SIDE 8192          /* canvas side */
+#define VSP_DET_CAND_CAPPED 1          /* more than max_candidates candidates */
+#define VSP_DET_FACES_CAPPED 2         /* more than max_faces faces survive the NMS */
+#define VSP_DET_NONFINITE 4            /* a candidate with a non-finite box or landmark was dropped */
+
+typedef struct vsp_det_src {
+  int64_t off;         /* byte offset of the (h, w, 3) RGB photo in `src`, rows of 3 w bytes without padding */
+  int32_t h, w;
+  int32_t slot;        /* image of the canvas batch it goes to */
+  int32_t pad_;
+} vsp_det_src;
+
+typedef struct vsp_det_face {
+  float box[4];        /* x1 y1 x2 y2, canvas pixels */
+  float score;
+  float lm[10];        /* x y of left eye, right eye, nose, left and right mouth corner */
+  int32_t prior;
+} vsp_det_face;
+
+int vsp_det_entry_u8(float* y, const uint8_t* src, size_t src_bytes, const vsp_det_src* items, const vsp_det_src* items_dev, int n,
+                     const float* w, const float* b, int B, int Hc, int Wc, int act, float slope, vsp_stream_t stream);
+int vsp_det_sep_f32(float* y, const float* x, const float* wd, const float* bd, const float* wp, const float* bp, int B, int Cin, int Cout,
+                    int H, int W, int stride, float slope, vsp_stream_t stream);
+int vsp_det_conv3x3_f32(float* y, const float* x, const float* w, const float* b, int B, int Cin, int Cout, int H, int W, int y_ch,
+                        int y_coff, int act, float slope, vsp_stream_t stream);
+int vsp_det_lateral_f32(float* y, const float* x, const float* w, const float* b, const float* up, int B, int Cin, int H, int W, int h2,
+                        int w2, int act, float slope, vsp_stream_t stream);
+int vsp_det_heads_f32(float* conf, float* loc, float* lm, const float* x, const float* w, const float* b, int B, int H, int W, int P,
+                      int p0, vsp_stream_t stream);
+/* priors of a canvas (0 for sides outside 1 .. VSP_DET_MAX_SIDE) */
+int vsp_det_priors(int Hc, int Wc);
+/* bytes of `work` for one call (0 for arguments outside the limits) */
+size_t vsp_det_work_bytes(int B, int Hc, int Wc, int max_candidates);
+int vsp_det_decode_nms_f32(vsp_det_face* faces, int32_t* info, uint8_t* work, size_t work_bytes, const float* conf, const float* loc,
+                           const float* lm, int B, int Hc, int Wc, float threshold, float nms, int max_candidates, int max_faces,
+                           vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

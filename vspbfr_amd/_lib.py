@@ -114,6 +114,14 @@ class PngItem(C.Structure):                  # vsp_png_item
     _fields_ = [("src_off", C.c_int64), ("out_off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("seg0", C.c_int32), ("row0", C.c_int32)]
 
 
+class DetSrc(C.Structure):                   # vsp_det_src
+    _fields_ = [("off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("slot", C.c_int32), ("pad_", C.c_int32)]
+
+
+class DetFace(C.Structure):                  # vsp_det_face
+    _fields_ = [("box", C.c_float * 4), ("score", C.c_float), ("lm", C.c_float * 10), ("prior", C.c_int32)]
+
+
 class JpegDecItem(C.Structure):
     _fields_ = [("in_off", C.c_int64), ("out_off", C.c_int64), ("work_off", C.c_int64)] + [
         (n, C.c_int32) for n in ("in_len", "h", "w", "subsampling", "restart", "interval0")]
@@ -218,6 +226,13 @@ SIGNATURES = {
     "vsp_jpeg_intervals": [_i, _i, _i, _i],
     "vsp_jpeg_encode_u8": [_p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p],
     "vsp_jpeg_decode_u8": [_p, C.c_size_t, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _p, _p, _i, _i, _p],
+    "vsp_det_entry_u8": [_p, _p, C.c_size_t, _p, _p, _i, _p, _p, _i, _i, _i, _i, _f, _p],
+    "vsp_det_sep_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vsp_det_conv3x3_f32": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vsp_det_lateral_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p],
+    "vsp_det_heads_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
+    "vsp_det_priors": [_i, _i],
+    "vsp_det_decode_nms_f32": [_p, _p, _p, C.c_size_t, _p, _p, _p, _i, _i, _i, _f, _f, _i, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
@@ -228,7 +243,7 @@ _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C
           "vsp_png_ragged_image_bound": [_i, _i, _i], "vsp_png_ragged_work_bytes": [_i64, _i64],
           "vsp_niqe_work_bytes": [_i, _i, _i, _i],
           "vsp_jpeg_interval_bound": [_i, _i], "vsp_jpeg_image_bound": [_i, _i, _i, _i],
-          "vsp_jpeg_decode_work_bytes": [_i, _i, _i, _i, _i, _i]}
+          "vsp_jpeg_decode_work_bytes": [_i, _i, _i, _i, _i, _i], "vsp_det_work_bytes": [_i, _i, _i, _i]}
 
 
 def _load():
@@ -253,7 +268,7 @@ def _load():
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
                       (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem),
-                      (13, ResampleDst), (14, PngItem)):
+                      (13, ResampleDst), (14, PngItem), (15, DetSrc), (16, DetFace)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

@@ -43,6 +43,8 @@ int vsp_struct_size(int which) {
     case 12: return (int)sizeof(vsp_jpeg_dec_item);
     case 13: return (int)sizeof(vsp_resample_dst);
     case 14: return (int)sizeof(vsp_png_item);
+    case 15: return (int)sizeof(vsp_det_src);
+    case 16: return (int)sizeof(vsp_det_face);
     default: return -1;
   }
 }

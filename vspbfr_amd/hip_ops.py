@@ -2071,6 +2071,118 @@ def color_fix_u8(crops, restored, mode, plan=None, items=None, tables=None, leve
     return out
 
 
+# ----------------------------------------------------------------------------------------------- face detection
+DET_MAX_CANDIDATES = 2048                    # include/vspbfr_hip.h VSP_DET_MAX_CANDIDATES
+DET_CAND_CAPPED, DET_FACES_CAPPED, DET_NONFINITE = 1, 2, 4      # VSP_DET_* status bits
+
+
+def det_priors(Hc, Wc):
+    """priors of an (Hc, Wc) canvas: 2 sum over steps 8, 16, 32 of ceil(Hc / s) ceil(Wc / s) (vsp_det_priors)"""
+    n = lib.vsp_det_priors(int(Hc), int(Wc))
+    if n <= 0:
+        raise RuntimeError(f"det_priors: canvas {(Hc, Wc)}")
+    return n
+
+
+def det_entry_u8(y, src, items, items_dev, n, w, b, Hc, Wc, slope=0.1):
+    """The detector's first layer on n u8 photos inside `src` (vsp_det_entry_u8): writes y[slot] (y is (B, 8, ceil(Hc/2), ceil(Wc/2)))
+    for the slots of `items` (a _lib.DetSrc array; items_dev the same bytes on the device).  w (3, 9, 8), b (8).  Returns y."""
+    _req(y, "y"), _u8(src, "src"), _u8(items_dev, "items_dev"), _req(w, "w"), _req(b, "b")
+    B = int(y.shape[0])
+    if y.dim() != 4 or tuple(y.shape[1:]) != (8, (Hc + 1) // 2, (Wc + 1) // 2) or w.numel() != 216 or b.numel() != 8:
+        raise RuntimeError(f"det_entry_u8: y {tuple(y.shape)} for a {(Hc, Wc)} canvas, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    if items_dev.numel() < n * C.sizeof(_lib.DetSrc):
+        raise RuntimeError("det_entry_u8: items_dev is shorter than the item table")
+    check(lib.vsp_det_entry_u8(_ptr(y), _ptr(src), src.numel(), C.cast(items, C.c_void_p), _ptr(items_dev), int(n), _ptr(w), _ptr(b), B,
+                               int(Hc), int(Wc), 1, float(slope), _stream()), "det_entry_u8")
+    return y
+
+
+def det_sep(x, wd, bd, wp, bp, stride=1, slope=0.1):
+    """One depthwise-separable block (vsp_det_sep_f32): x (B, Cin, H, W), wd (Cin, 9), bd (Cin), wp (Cin, Cout), bp (Cout) ->
+    (B, Cout, OH, OW), LeakyReLU(slope) behind both convolutions."""
+    for t, nm in ((x, "x"), (wd, "wd"), (bd, "bd"), (wp, "wp"), (bp, "bp")):
+        _req(t, nm)
+    B, Cin, H, W = (int(v) for v in x.shape)
+    Cout = int(wp.shape[1]) if wp.dim() == 2 else -1
+    if tuple(wd.shape) != (Cin, 9) or tuple(bd.shape) != (Cin,) or tuple(wp.shape) != (Cin, Cout) or tuple(bp.shape) != (Cout,):
+        raise RuntimeError(f"det_sep: x {tuple(x.shape)}, wd {tuple(wd.shape)}, bd {tuple(bd.shape)}, wp {tuple(wp.shape)}, bp {tuple(bp.shape)}")
+    if stride not in (1, 2):
+        raise RuntimeError(f"det_sep: stride {stride}")
+    y = torch.empty((B, Cout, (H - 1) // stride + 1, (W - 1) // stride + 1), device=x.device, dtype=torch.float32)
+    check(lib.vsp_det_sep_f32(_ptr(y), _ptr(x), _ptr(wd), _ptr(bd), _ptr(wp), _ptr(bp), B, Cin, Cout, H, W, int(stride), float(slope),
+                              _stream()), "det_sep")
+    return y
+
+
+def det_conv3x3(x, w, b, slope=None, out=None, y_coff=0):
+    """Dense 3x3, stride 1, pad 1 (vsp_det_conv3x3_f32): x (B, Cin, H, W), w (Cin, 9, Cout), b (Cout).  slope None: no activation,
+    else LeakyReLU(slope) (0: ReLU).  out: None (a new (B, Cout, H, W)) or a (B, C, H, W) tensor whose channels y_coff.. take the result."""
+    _req(x, "x"), _req(w, "w"), _req(b, "b")
+    B, Cin, H, W = (int(v) for v in x.shape)
+    if w.dim() != 3 or tuple(w.shape[:2]) != (Cin, 9) or tuple(b.shape) != (int(w.shape[2]),):
+        raise RuntimeError(f"det_conv3x3: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    Cout = int(w.shape[2])
+    if out is None:
+        out = torch.empty((B, Cout, H, W), device=x.device, dtype=torch.float32)
+    _req(out, "out")
+    if out.dim() != 4 or (int(out.shape[0]), int(out.shape[2]), int(out.shape[3])) != (B, H, W):
+        raise RuntimeError(f"det_conv3x3: out {tuple(out.shape)} for x {tuple(x.shape)}")
+    check(lib.vsp_det_conv3x3_f32(_ptr(out), _ptr(x), _ptr(w), _ptr(b), B, Cin, Cout, H, W, int(out.shape[1]), int(y_coff),
+                                  0 if slope is None else 1, 0.0 if slope is None else float(slope), _stream()), "det_conv3x3")
+    return out
+
+
+def det_lateral(x, w, b, up=None, slope=0.1):
+    """1x1 to 64 channels, LeakyReLU(slope), plus the nearest upsampling (source index floor(i in / out)) of `up` (B, 64, h2, w2)
+    (vsp_det_lateral_f32): x (B, Cin, H, W), w (Cin, 64), b (64) -> (B, 64, H, W)."""
+    _req(x, "x"), _req(w, "w"), _req(b, "b"), _opt(up, "up")
+    B, Cin, H, W = (int(v) for v in x.shape)
+    if tuple(w.shape) != (Cin, 64) or tuple(b.shape) != (64,):
+        raise RuntimeError(f"det_lateral: x {tuple(x.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    h2 = w2 = 0
+    if up is not None:
+        if up.dim() != 4 or tuple(up.shape[:2]) != (B, 64):
+            raise RuntimeError(f"det_lateral: up {tuple(up.shape)}")
+        h2, w2 = int(up.shape[2]), int(up.shape[3])
+    y = torch.empty((B, 64, H, W), device=x.device, dtype=torch.float32)
+    check(lib.vsp_det_lateral_f32(_ptr(y), _ptr(x), _ptr(w), _ptr(b), _ptr(up), B, Cin, H, W, h2, w2, 1, float(slope), _stream()),
+          "det_lateral")
+    return y
+
+
+def det_heads(x, w, b, conf, loc, lm, p0):
+    """The class, box and landmark heads of one level (vsp_det_heads_f32): x (B, 64, H, W), w (64, 32), b (32) -> priors p0 .. p0 + 2 H W
+    - 1 of conf (B, P, 2), loc (B, P, 4), lm (B, P, 10)."""
+    for t, nm in ((x, "x"), (w, "w"), (b, "b"), (conf, "conf"), (loc, "loc"), (lm, "lm")):
+        _req(t, nm)
+    B, Cin, H, W = (int(v) for v in x.shape)
+    P = int(conf.shape[1]) if conf.dim() == 3 else -1
+    if Cin != 64 or tuple(w.shape) != (64, 32) or tuple(b.shape) != (32,) or tuple(conf.shape) != (B, P, 2) or tuple(loc.shape) != (B, P, 4) \
+            or tuple(lm.shape) != (B, P, 10):
+        raise RuntimeError(f"det_heads: x {tuple(x.shape)}, w {tuple(w.shape)}, conf {tuple(conf.shape)}, loc {tuple(loc.shape)}, lm {tuple(lm.shape)}")
+    check(lib.vsp_det_heads_f32(_ptr(conf), _ptr(loc), _ptr(lm), _ptr(x), _ptr(w), _ptr(b), B, H, W, P, int(p0), _stream()), "det_heads")
+
+
+def det_decode_nms(conf, loc, lm, Hc, Wc, threshold=0.8, nms=0.4, max_candidates=1024, max_faces=256):
+    """Decode, candidate selection and greedy NMS per image on the device (vsp_det_decode_nms_f32): conf (B, P, 2), loc (B, P, 4), lm
+    (B, P, 10) for the P priors of an (Hc, Wc) canvas -> (faces: uint8 (B, max_faces, 64) holding _lib.DetFace records, zero past the
+    count; info: int32 (B, 4) = faces written, status bits DET_*, candidates before the cap, non-finite candidates dropped)."""
+    _req(conf, "conf"), _req(loc, "loc"), _req(lm, "lm")
+    P = det_priors(Hc, Wc)
+    B = int(conf.shape[0])
+    if tuple(conf.shape) != (B, P, 2) or tuple(loc.shape) != (B, P, 4) or tuple(lm.shape) != (B, P, 10):
+        raise RuntimeError(f"det_decode_nms: conf {tuple(conf.shape)}, loc {tuple(loc.shape)}, lm {tuple(lm.shape)} for {P} priors")
+    max_candidates, max_faces = int(max_candidates), int(max_faces)
+    faces = torch.zeros((B, max(max_faces, 1), 64), device=conf.device, dtype=torch.uint8)
+    info = torch.zeros((B, 4), device=conf.device, dtype=torch.int32)
+    nbytes = lib.vsp_det_work_bytes(max(B, 1), int(Hc), int(Wc), max_candidates)
+    work = torch.empty(max(nbytes, 16), device=conf.device, dtype=torch.uint8)
+    check(lib.vsp_det_decode_nms_f32(_ptr(faces), _ptr(info), _ptr(work), work.numel(), _ptr(conf), _ptr(loc), _ptr(lm), B, int(Hc), int(Wc),
+                                     float(threshold), float(nms), max_candidates, max_faces, _stream()), "det_decode_nms")
+    return faces, info
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types
