@@ -42,7 +42,8 @@ int vsp_device_count(void);
 /* sizeof of an ABI struct (0 = vsp_fir_epilogue, 1 = vsp_conv_params, 2 = vsp_gemm_params,
  * 3 = vsp_tacc_block, 4 = vsp_tacc_chain_params, 5 = vsp_conv_wgrad_params, 6 = vsp_degrade_item, 7 = vsp_resample_item,
  * 8 = vsp_face_item, 9 = vsp_face_tile, 10 = vsp_face_aa_item, 11 = vsp_jpeg_item, 12 = vsp_jpeg_dec_item,
- * 13 = vsp_resample_dst, 14 = vsp_png_item): lets a binding in
+ * 13 = vsp_resample_dst, 14 = vsp_png_item, 15 = vsp_det_src, 16 = vsp_det_face,
+ * 17 = vsp_sr_item): lets a binding in
  * another language check its own struct layout when it loads the library. */
 int vsp_struct_size(int which);
 
@@ -1213,6 +1214,48 @@ size_t vsp_det_work_bytes(int B, int Hc, int Wc, int max_candidates);
 int vsp_det_decode_nms_f32(vsp_det_face* faces, int32_t* info, uint8_t* work, size_t work_bytes, const float* conf, const float* loc,
                            const float* lm, int B, int Hc, int Wc, float threshold, float nms, int max_candidates, int max_faces,
                            vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Background upscaling for whole photos (csrc/sr.hip): Real-ESRGAN's compact network (SRVGGNetCompact, 64 features) with
+ * f16 operands and fp32 accumulation.  Activations are (h, w, 64) _Float16 per item, the items of a group back to back in a buffer of
+ * act_bytes; one launch per layer serves the whole ragged group through the item table (`items` on the host for the checks,
+ * `items_dev` the same bytes on the device).  The tile list (VSP_SR_TILE_H rows x VSP_SR_TILE_W columns) runs across the items:
+ * items[i].tile0 = sum over j < i of ceil(h_j / VSP_SR_TILE_H) ceil(w_j / VSP_SR_TILE_W).
+ *   head   y = PReLU(conv3x3(src / 255) + b): 3 -> 64, zero padding, fp32 fmaf; w is (27, 64) fp32, row (3 ky + kx) 3 + c.
+ *   body   y = PReLU(conv3x3(x) + b): 64 -> 64 on v_mfma_f32_16x16x32_f16; b, slope fp32 (64); y must not be x.
+ *          w_img: the f16 image of upscale.pack_body_weight, 18 x NB x 64 x 8 halves (NB = 4): element j of lane l of block nb of
+ *          K-step s = w[co = 16 nb + (l & 15)][ci = 32 (s & 1) + 8 (l >> 4) + j][ky = (s >> 1) / 3][kx = (s >> 1) % 3].
+ *   tail   v = conv3x3(x) + b + src / 255 of the pixel the output pixel lies in: 64 -> 3 scale^2, channel c scale^2 + dy scale + dx ->
+ *          output pixel (scale y + dy, scale x + dx), colour c; w_img as the body's with NB = 1 (scale 2) or 3 (scale 4), the channels
+ *          past 3 scale^2 zero, b padded to 16 NB.  out byte = rintf(255 clamp(v, 0, 1)); rows keep0 .. keep0 + keepn - 1 of the item
+ *          are written, row keep0 at out_off, rows of 3 scale w bytes.  A non-finite v is written as 0 and ORs VSP_SR_NONFINITE into
+ *          info[slot] (the caller zeroes info).  out_f32 (or null): v itself at the same element index as the byte.
+ * VSP_EINVAL, nothing launched: a null pointer, a scale other than 2 or 4, h or w < 1, an item outside one of its buffers, rows outside
+ * the item, a slot outside 0 .. n_info - 1, a tile0 that is not the running tile count, more than VSP_SR_MAX_ITEMS items, a buffer
+ * that is not 16-byte aligned.  VSP_ENOTSUP: a buffer of 2 GiB or more.  n = 0 returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_SR_TILE_H 8
+#define VSP_SR_TILE_W 32
+#define VSP_SR_MAX_ITEMS 65536
+#define VSP_SR_NONFINITE 1             /* info bit: a value was not finite before the clamp */
+
+typedef struct vsp_sr_item {
+  int64_t src_off;     /* byte offset of the item's (h, w, 3) RGB rows in `src`, rows of 3 w bytes without padding */
+  int64_t act_off;     /* pixel offset of the item's (h, w, 64) activation in the activation buffers */
+  int64_t out_off;     /* tail: byte offset in `out` of output row scale keep0 of the item */
+  int32_t h, w;
+  int32_t keep0, keepn; /* tail: the item's rows that are written (a band's rows without its halo) */
+  int32_t tile0;       /* first tile of the item in the launch's tile list */
+  int32_t slot;        /* tail: index of the item's info word */
+} vsp_sr_item;
+
+int vsp_sr_head_u8(void* y, size_t act_bytes, const uint8_t* src, size_t src_bytes, const vsp_sr_item* items, const vsp_sr_item* items_dev,
+                   int n, const float* w, const float* b, const float* slope, vsp_stream_t stream);
+int vsp_sr_body_f16(void* y, const void* x, size_t act_bytes, const vsp_sr_item* items, const vsp_sr_item* items_dev, int n,
+                    const void* w_img, const float* b, const float* slope, vsp_stream_t stream);
+int vsp_sr_tail_u8(uint8_t* out, size_t out_bytes, float* out_f32, int32_t* info, int n_info, const void* x, size_t act_bytes,
+                   const uint8_t* src, size_t src_bytes, const vsp_sr_item* items, const vsp_sr_item* items_dev, int n, const void* w_img,
+                   const float* b, int scale, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -118,6 +118,11 @@ class DetSrc(C.Structure):                   # vsp_det_src
     _fields_ = [("off", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("slot", C.c_int32), ("pad_", C.c_int32)]
 
 
+class SrItem(C.Structure):                   # vsp_sr_item
+    _fields_ = [("src_off", C.c_int64), ("act_off", C.c_int64), ("out_off", C.c_int64)] + [
+        (n, C.c_int32) for n in ("h", "w", "keep0", "keepn", "tile0", "slot")]
+
+
 class DetFace(C.Structure):                  # vsp_det_face
     _fields_ = [("box", C.c_float * 4), ("score", C.c_float), ("lm", C.c_float * 10), ("prior", C.c_int32)]
 
@@ -233,6 +238,9 @@ SIGNATURES = {
     "vsp_det_heads_f32": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     "vsp_det_priors": [_i, _i],
     "vsp_det_decode_nms_f32": [_p, _p, _p, C.c_size_t, _p, _p, _p, _i, _i, _i, _f, _f, _i, _i, _p],
+    "vsp_sr_head_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _p, _p, _p, _p],
+    "vsp_sr_body_f16": [_p, _p, C.c_size_t, _p, _p, _i, _p, _p, _p, _p],
+    "vsp_sr_tail_u8": [_p, C.c_size_t, _p, _p, _i, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _p, _p, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
@@ -268,7 +276,7 @@ def _load():
         raise ImportError(f"vspbfr_amd: ABI version {lib.vsp_abi_version()} != {ABI_VERSION}")
     for which, st in ((0, FirEpilogue), (1, ConvParams), (2, GemmParams), (3, TaccBlock), (4, TaccChainParams),
                       (5, ConvWgradParams), (6, DegradeItem), (7, ResampleItem), (8, FaceItem), (9, FaceTile), (10, FaceAAItem), (11, JpegItem), (12, JpegDecItem),
-                      (13, ResampleDst), (14, PngItem), (15, DetSrc), (16, DetFace)):
+                      (13, ResampleDst), (14, PngItem), (15, DetSrc), (16, DetFace), (17, SrItem)):
         if lib.vsp_struct_size(which) != C.sizeof(st):
             raise ImportError(f"vspbfr_amd: struct layout mismatch for {st.__name__}: "
                               f"C {lib.vsp_struct_size(which)} vs ctypes {C.sizeof(st)}")

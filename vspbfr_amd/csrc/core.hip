@@ -45,6 +45,7 @@ int vsp_struct_size(int which) {
     case 14: return (int)sizeof(vsp_png_item);
     case 15: return (int)sizeof(vsp_det_src);
     case 16: return (int)sizeof(vsp_det_face);
+    case 17: return (int)sizeof(vsp_sr_item);
     default: return -1;
   }
 }

@@ -2183,6 +2183,60 @@ def det_decode_nms(conf, loc, lm, Hc, Wc, threshold=0.8, nms=0.4, max_candidates
     return faces, info
 
 
+SR_TILE_H, SR_TILE_W, SR_NONFINITE = 8, 32, 1      # include/vspbfr_hip.h VSP_SR_TILE_*, VSP_SR_NONFINITE
+_TWO_GIB = 1 << 31
+
+
+def _sr_act(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16 or t.dim() != 1 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a flat contiguous CUDA float16 tensor")
+    return t
+
+
+def sr_head_u8(y, src, items, items_dev, n, w, b, slope):
+    """The upscaler's first layer on the u8 photos of a group where they lie in `src` (vsp_sr_head_u8): y, a flat float16 buffer, takes
+    PReLU(conv3x3(src / 255) + b) as (h, w, 64) per item at items[i].act_off pixels.  items: a _lib.SrItem array, items_dev the same
+    bytes on the device.  w (27, 64), b (64), slope (64) float32.  Returns y."""
+    _sr_act(y, "y"), _u8(src, "src"), _u8(items_dev, "items_dev"), _req(w, "w"), _req(b, "b"), _req(slope, "slope")
+    if w.numel() != 27 * 64 or b.numel() != 64 or slope.numel() != 64 or items_dev.numel() < n * C.sizeof(_lib.SrItem):
+        raise RuntimeError(f"sr_head_u8: w {tuple(w.shape)}, b {tuple(b.shape)}, slope {tuple(slope.shape)}, items_dev of {items_dev.numel()} bytes")
+    check(lib.vsp_sr_head_u8(_ptr(y), y.numel() * 2, _ptr(src), src.numel(), C.cast(items, C.c_void_p), _ptr(items_dev), int(n), _ptr(w),
+                             _ptr(b), _ptr(slope), _stream()), "sr_head_u8")
+    return y
+
+
+def sr_body_f16(y, x, items, items_dev, n, w_img, b, slope):
+    """One body layer of the upscaler over a group (vsp_sr_body_f16): y = PReLU(conv3x3(x) + b), x and y flat float16 buffers of one size
+    holding (h, w, 64) per item; w_img the float16 image of upscale.pack_body_weight (18, 4, 64, 8), b and slope float32 (64)."""
+    _sr_act(y, "y"), _sr_act(x, "x"), _u8(items_dev, "items_dev"), _req(b, "b"), _req(slope, "slope")
+    if y.numel() != x.numel() or not isinstance(w_img, torch.Tensor) or w_img.dtype != torch.float16 or not w_img.is_contiguous() \
+            or w_img.numel() != 18 * 4 * 64 * 8 or b.numel() != 64 or slope.numel() != 64 or items_dev.numel() < n * C.sizeof(_lib.SrItem):
+        raise RuntimeError("sr_body_f16: x and y of one size, w_img a float16 image of 18 x 4 x 64 x 8, b and slope of 64")
+    check(lib.vsp_sr_body_f16(_ptr(y), _ptr(x), x.numel() * 2, C.cast(items, C.c_void_p), _ptr(items_dev), int(n), _ptr(w_img), _ptr(b),
+                              _ptr(slope), _stream()), "sr_body_f16")
+    return y
+
+
+def sr_tail_u8(out, info, x, src, items, items_dev, n, w_img, b, scale, out_f32=None):
+    """The upscaler's last layer over a group (vsp_sr_tail_u8): conv3x3 64 -> 3 scale^2, + b, pixel shuffle, + src / 255, clamp, u8 into
+    the flat uint8 `out` at items[i].out_off; info (int32, zeroed by the caller) takes SR_NONFINITE at items[i].slot.  w_img: float16
+    (18, NB, 64, 8) with NB = 1 (scale 2) or 3 (scale 4), b float32 (16 NB).  out_f32: a flat float32 tensor of out's size or None."""
+    _u8(out, "out"), _sr_act(x, "x"), _u8(src, "src"), _u8(items_dev, "items_dev"), _req(b, "b"), _opt(out_f32, "out_f32")
+    nb = {2: 1, 4: 3}.get(int(scale), 0)
+    if not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or not info.is_cuda or not info.is_contiguous():
+        raise RuntimeError("sr_tail_u8: info must be a contiguous CUDA int32 tensor")
+    if nb and (not isinstance(w_img, torch.Tensor) or w_img.dtype != torch.float16 or not w_img.is_contiguous()
+               or w_img.numel() != 18 * nb * 64 * 8 or b.numel() != 16 * nb):
+        raise RuntimeError(f"sr_tail_u8: scale {scale} takes a float16 image of 18 x {nb} x 64 x 8 and {16 * nb} biases")
+    if out_f32 is not None and out_f32.numel() != out.numel():
+        raise RuntimeError("sr_tail_u8: out_f32 must have one float per byte of out")
+    if items_dev.numel() < n * C.sizeof(_lib.SrItem):
+        raise RuntimeError("sr_tail_u8: items_dev is shorter than the item table")
+    check(lib.vsp_sr_tail_u8(_ptr(out), out.numel(), _ptr(out_f32), _ptr(info), info.numel(), _ptr(x), x.numel() * 2, _ptr(src), src.numel(),
+                             C.cast(items, C.c_void_p), _ptr(items_dev), int(n), _ptr(w_img), _ptr(b), int(scale), _stream()), "sr_tail_u8")
+    return out
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types

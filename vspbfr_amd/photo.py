@@ -373,14 +373,25 @@ class FacePlan:
                 self._dev[1]["photos"] = self.device_photos
         return self._dev[1]
 
-    def background(self, device):
+    def background(self, device, upscaler=None):
         """The packed output photos before any face is pasted, a fresh device uint8 buffer of out_bytes: the photos themselves at upscale
         1, else each photo resized to exactly (upscale w, upscale h) -- by the device LANCZOS kernel where resample.kernel_serves takes
         it, by PIL otherwise; both are Pillow's bytes.  The group is ONE ragged plan (resample.ResamplePlan with out_sizes) whose
         source is the plan's device `photos` section and whose destinations are the photos' places in the output: one launch pair,
-        and no pixel leaves the device but those of a photo the kernel does not serve."""
+        and no pixel leaves the device but those of a photo the kernel does not serve.
+
+        upscaler (an upscale.SrUpscaler): the photos go through the network instead -- straight to out_off where its scale is
+        the plan's, through one ragged LANCZOS resize of its x4 output at upscale 2; upscale 1 or a network below the plan's upscale is
+        a ValueError.  `self.background_info` is then upscale()'s info.  None: nothing changes."""
         import torch
         dev = self.upload(device)
+        if upscaler is not None:
+            if self.upscale not in (2, 4) or upscaler.scale < self.upscale:
+                raise ValueError(f"FacePlan.background: a x{upscaler.scale} network cannot fill an upscale of {self.upscale}")
+            out = torch.empty(self.out_bytes, dtype=torch.uint8, device=dev["photos"].device)
+            out, self.background_info = upscaler.upscale_to(self.upscale, device_photos=(dev["photos"], self.src_off, self.shapes), out=out,
+                                                            out_offsets=self.out_off)
+            return out
         if self.upscale == 1:
             return dev["photos"].clone()
         from .resample import ResamplePlan
@@ -463,12 +474,16 @@ class PhotoRestorer:
     `pipe` (a RestorationPipeline) over the faces of all photos in batches of `batch`, quantisation to uint8 as PngWriter does
     (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4.
     antialias=True: the anti-aliased entries for crop and paste.  color_fix="stats" or "wavelet": the restored crops take
-    their colours back from the crops (vsp_color_fix_u8) and the fixed crops are pasted."""
+    their colours back from the crops (vsp_color_fix_u8) and the fixed crops are pasted.  background: an upscale.SrUpscaler
+    whose output replaces the LANCZOS resize under the faces (upscale 2 or 4, at most the network's scale)."""
 
     def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER,
-                 antialias=False, color_fix=None, color_levels=5):
+                 antialias=False, color_fix=None, color_levels=5, background=None):
         if int(upscale) not in (1, 2, 4) or int(batch) < 1:
             raise ValueError(f"PhotoRestorer: batch {batch}, upscale {upscale}")
+        if background is not None and (int(upscale) == 1 or background.scale < int(upscale)):
+            raise ValueError(f"PhotoRestorer: a x{background.scale} background network cannot fill an upscale of {upscale}")
+        self.background = background           # an upscale.SrUpscaler that fills the output photos instead of the LANCZOS resize (DESIGN 23)
         self.pipe, self.batch, self.upscale, self.size, self.border = pipe, int(batch), int(upscale), int(size), tuple(border)
         self.antialias = bool(antialias)       # minified faces through the tent filter of DESIGN 16, crop and paste
         self.ramp = default_ramp(inset, feather)
@@ -488,7 +503,7 @@ class PhotoRestorer:
         S = self.size
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)
-            plan.out_packed = plan.background(device)
+            plan.out_packed = plan.background(device) if self.background is None else plan.background(device, self.background)
             head = (plan.split(plan.out_packed), empty, empty, plan)
             return head if self.color_fix is None else head + (empty,)
         crops, low = crop_faces(plan, device, u8=True, f32=True, border=self.border)
@@ -498,9 +513,10 @@ class PhotoRestorer:
                 out = self.pipe(low[i:i + self.batch])
                 restored.append(hip_ops.quantize_u8_nhwc(out["restored"].contiguous(), -1.0, 1.0))
         restored = torch.cat(restored) if len(restored) > 1 else restored[0]
+        bg = None if self.background is None else plan.background(device, self.background)
         if self.color_fix is None:
-            out = plan.out_packed = paste_faces(plan, restored, device, self.ramp)
+            out = plan.out_packed = paste_faces(plan, restored, device, self.ramp, out=bg)
             return plan.split(out), crops, restored, plan
         fixed = color_fix(crops, restored, self.color_fix, plan, device, self.color_levels)
-        out = plan.out_packed = paste_faces(plan, fixed, device, self.ramp)
+        out = plan.out_packed = paste_faces(plan, fixed, device, self.ramp, out=bg)
         return plan.split(out), crops, restored, plan, fixed

@@ -4,7 +4,7 @@
         [--save_faces] [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L]
         [--detect_threshold 0.8] [--detect_nms 0.4] [--detect_side 1024] [--detect_max_faces N] [--detect_min_face PX]
         [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] [--decode {host,device}]
-        [--png_encode {host,device}] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--png_encode {host,device}] [--bg_weights W [--bg_band_rows N]] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  Exactly one of
@@ -54,6 +54,13 @@ photos goes through one detect() call (with --decode device on the decoder's buf
 would refuse (degenerate landmarks, with --antialias a minification above 16) is dropped and listed with its reason.  report.json then
 lists `detect` (the parameters) and per photo `score`, `box` and, if any, `dropped`; OUT/landmarks.json (landmarks_<rank>.json in a
 multi-GPU run) holds the faces that were used, in the format --landmarks reads.  Without the flag nothing changes.
+
+--bg_weights W: with --upscale 2 or 4 the photo under the faces is upscaled by Real-ESRGAN's compact network (vspbfr_amd.upscale,
+csrc/sr.hip) from the checkpoint W instead of the LANCZOS resize -- no weights are shipped, and the key layout the loader
+expects is unverified against a real file.  A x4 network at --upscale 2 goes through the device LANCZOS resize down from its x4 output;
+a x2 network at --upscale 4 is refused.  --bg_band_rows N processes every photo in bands of N rows (the same bytes).  report.json then
+lists `background` = {model, num_conv, scale, banded, nonfinite}; `nonfinite` names the photos in which a value was not finite before the
+clamp (written as 0): a warning, not an abort.  Without the flag nothing changes.
 
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
@@ -153,6 +160,7 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
     ext = ".jpg" if jpg else ".png"
     ragged = png_device and not jpg          # a group's photos go through one call of the ragged PNG encoder
     report, found = [], {}
+    bg_banded, bg_nonfinite = False, []
     if detector is not None:
         landmarks = {}
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
@@ -171,6 +179,10 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
                 detect_group(detector, detect_params, group, landmarks, found, photos=photos, size=args.size, upscale=args.upscale,
                              antialias=getattr(args, "antialias", False))
             outs, crops, restored, plan, *fixed = restorer(photos, [landmarks.get(n) for n in group], device, names=group)
+        if restorer.background is not None:
+            info = plan.background_info
+            bg_banded = bg_banded or any(info["banded"])
+            bg_nonfinite += [n for n, f in zip(group, info["flags"].cpu().tolist()) if f]
         stems = [os.path.join(args.out, os.path.splitext(n)[0]) for n in group]
         for stem in stems:
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
@@ -210,6 +222,10 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
         head.update(format="jpg", quality=args.quality, subsampling=args.subsampling)
     if getattr(args, "png_encode", None) is not None:
         head.update(png_encode=args.png_encode)
+    if restorer.background is not None:
+        head.update(background=restorer.background.describe(bg_banded, bg_nonfinite))
+        if bg_nonfinite:
+            print("warning: non-finite background values were written as 0 in: " + ", ".join(bg_nonfinite))
     if detector is not None:
         from .detect import write_landmarks
         head.update(detect=detect_params)
@@ -259,7 +275,16 @@ def main(argv=None):
                     help="decode baseline JPEG inputs on the device or everything with Pillow on the host (the default); equal bytes")
     ap.add_argument("--png_encode", choices=["host", "device"], default=None,
                     help="code the PNG files with Pillow on the host (the default) or on the device; equal pixels")
+    ap.add_argument("--bg_weights", type=str, default=None,
+                    help="SRVGGNetCompact checkpoint (not shipped): upscale the photo under the faces with it instead of LANCZOS; needs --upscale 2 or 4")
+    ap.add_argument("--bg_band_rows", type=int, default=None, help="--bg_weights: process every photo in bands of this many rows (the same bytes)")
     args = ap.parse_args(argv)
+    bg_state = None
+    if args.bg_weights is not None:
+        from .upscale import check_background_arguments
+        bg_state = check_background_arguments(ap, args.bg_weights, args.upscale, args.bg_band_rows)
+    elif args.bg_band_rows is not None:
+        ap.error("--bg_band_rows belongs to --bg_weights")
     if (args.landmarks is None) == (args.detect_weights is None):
         ap.error("exactly one of --landmarks and --detect_weights must be given")
     detect_params = None
@@ -310,6 +335,9 @@ def main(argv=None):
     pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)
     restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather,
                              antialias=args.antialias, color_fix=color_fix, color_levels=color_levels)
+    if bg_state is not None:
+        from .upscale import SrUpscaler
+        restorer.background = SrUpscaler(bg_state, device, band_rows=args.bg_band_rows)
     detector = None
     if args.detect_weights is not None:
         try:
