@@ -452,7 +452,9 @@ int vsp_add3_f32(float* out, const float* a, const float* b, const float* c, int
  *       (models/RestoreNet.py:100-118), evaluated inside the kernel: the skip image is never materialised at full size
  *   Cin <= 4 (the 3 -> 64 input layer, two FusedLeakyReLUs in the epilogue, models/RestoreNet.py:725-787 with k = 1):
  *       y[b,co,p] = act2(act1(sum_ci x[b,ci,p] * w[co,ci] * in_scale[b,ci] + ch_bias[co])),  act_i(v) = lrelu(v + bias_i[co], 0.2) * sqrt2
- * x (B,Cin,HW), y / res (B,Cout,HW) dense, W = row length; in_scale, ch_bias, bias1, bias2, res, up_src may be NULL. */
+ * x (B,Cin,HW), y / res (B,Cout,HW) dense, W = row length; in_scale, ch_bias, bias1, bias2, res, up_src may be NULL.
+ * The weights of a launch sit in 64 KB of LDS: Cout * Cin <= 16384 on the few-output side (Cin <= 4096 at Cout = 4), Cout * (Cin + 3)
+ * <= 16384 on the few-input side (Cout <= 2340 at Cin = 4); anything wider is VSP_EINVAL before any launch. */
 int vsp_pointwise_f32(float* y, const float* x, const float* w, const float* in_scale, const float* ch_bias,
                       const float* bias1, int act1, const float* bias2, int act2, const float* res, const float* up_src,
                       const float* up_kernel, int W, int B, int Cin, int Cout, int64_t HW, vsp_stream_t stream);

@@ -229,6 +229,12 @@ __global__ __launch_bounds__(256) void pw_few_in_kernel(TY* __restrict__ y, cons
 
 }  // namespace
 
+// The weights of one launch (few outputs: Cout x Cin, few inputs: Cout x (Cin + 3)) live in dynamic LDS.  Neither kernel raises
+// hipFuncAttributeMaxDynamicSharedMemorySize, so what can launch is what fits the default 64 KB -- the entry admits exactly that (the
+// widest layers of the path are 512 -> 3 and 3 -> 64: 6 KB and 1.5 KB; above 64 KB a stream kernel would be down to one or two
+// workgroups per CU, nothing to spend 16 per-instantiation attribute flags on).
+static constexpr size_t kMaxLds = 64 * 1024;
+
 // W = element type of the wide side: x when Cout <= 4, y when Cin <= 4 (the other side and every operand are fp32)
 template <typename TW>
 static int pointwise_impl(void* y, const void* x, const float* w, const float* in_scale, const float* ch_bias,
@@ -248,8 +254,9 @@ static int pointwise_impl(void* y, const void* x, const float* w, const float* i
               "pointwise: the up-sampled residual needs the few-output form, a 4x4 kernel and even H, W");
   if (Cout <= 4) {
     VSP_REQUIRE(!act1 && !act2, "pointwise: activations are only implemented on the few-input-channels form");
-    VSP_REQUIRE(Cin <= 8192, "pointwise: too many input channels");
     const size_t lds = (size_t)Cout * Cin * sizeof(float);
+    VSP_REQUIRE(lds <= kMaxLds, "pointwise: %d x %d weights need %zu bytes of LDS, the limit is %zu (Cin <= %d at Cout = %d)", Cout, Cin, lds,
+                kMaxLds, (int)(kMaxLds / sizeof(float)) / Cout, Cout);
     float* yf = static_cast<float*>(y);
     const TW* xw = static_cast<const TW*>(x);
     switch (Cout) {
@@ -260,8 +267,9 @@ static int pointwise_impl(void* y, const void* x, const float* w, const float* i
     }
   } else {
     VSP_REQUIRE(!res, "pointwise: a residual is only implemented on the few-output-channels form");
-    VSP_REQUIRE(Cout <= 4096, "pointwise: too many output channels");
     const size_t lds = (size_t)Cout * (Cin + 3) * sizeof(float);
+    VSP_REQUIRE(lds <= kMaxLds, "pointwise: %d x (%d + 3) weights and biases need %zu bytes of LDS, the limit is %zu (Cout <= %d at Cin = %d)", Cout,
+                Cin, lds, kMaxLds, (int)(kMaxLds / sizeof(float)) / (Cin + 3), Cin);
     TW* yw = static_cast<TW*>(y);
     const float* xf = static_cast<const float*>(x);
     switch (Cin) {
