@@ -996,6 +996,25 @@ int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* cro
                          const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
                          size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, vsp_stream_t stream);
 
+/* The two paste entries with a face-parsing mask: the arguments, checks and arithmetic of vsp_face_paste_u8 /
+ * vsp_face_paste_aa_u8, and `mask_dev`: face i's (S, S) uint16 paste weights 0 .. 256 at element i S S of a device buffer of mask_elems
+ * elements (vsp_parse_blur_u16 writes them; the host never reads them).  At a pixel with Q5 crop coordinates (X, Y) the mask is sampled
+ * with the four 5-bit taps of the colour, wm = (sum 32 wx wy m + 16384) >> 15, taps past the crop clamped, and the blend weight is
+ * w = (ramp[...] wm + 128) >> 8; a mask of all 256 gives the bytes of the unmasked entry.  The anti-aliased entry keeps the tent filter
+ * for the colour and the four taps for the mask; wm is clamped to 256, so a weight above 256 acts as 256.  VSP_EINVAL besides the
+ * unmasked entries': a null or misaligned mask, fewer than n S S elements.  VSP_ENOTSUP: a mask of 2 GiB or more. */
+int vsp_face_paste_mask_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                           const int32_t* tables_dev, size_t table_ints, const vsp_face_item* items, const vsp_face_item* items_dev, int n, int S,
+                           const vsp_face_tile* tiles, const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces,
+                           const int32_t* tile_faces_dev, size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len,
+                           const uint16_t* mask_dev, size_t mask_elems, vsp_stream_t stream);
+int vsp_face_paste_mask_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                              const int32_t* tables_dev, size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints,
+                              const vsp_face_aa_item* items, const vsp_face_aa_item* items_dev, int n, int S, const vsp_face_tile* tiles,
+                              const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
+                              size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, const uint16_t* mask_dev,
+                              size_t mask_elems, vsp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Colour fix for restored faces (csrc/color_fix.hip; bytes equal tests/color_fix_ref.py).  crop, restored, out: packed
  * uint8 (F, S, S, 3) on the device; out may be `restored` itself (any other overlap of out with an input is VSP_EINVAL).  Integer
@@ -1258,6 +1277,44 @@ int vsp_sr_body_f16(void* y, const void* x, size_t act_bytes, const vsp_sr_item*
 int vsp_sr_tail_u8(uint8_t* out, size_t out_bytes, float* out_f32, int32_t* info, int n_info, const void* x, size_t act_bytes,
                    const uint8_t* src, size_t src_bytes, const vsp_sr_item* items, const vsp_sr_item* items_dev, int n, const void* w_img,
                    const float* b, int scale, vsp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Face-parsing paste masks for whole photos (csrc/parse.hip): facexlib's ParseNet with f16 operands and fp32 accumulation,
+ * and the integer blur that turns its class map into paste weights.  Activations are (F, H, W, C) _Float16, the faces of a call back
+ * to back; every convolution is 3x3 behind a reflection padding of 1 (index -1 -> 1, H -> H - 2), so H, W >= 2 everywhere.
+ *   head   y = conv3x3((crops / 255 - 0.5) / 0.5) + b: 3 -> 64, fp32 fmaf; crops (F, H, W, 3) u8; w (27, 64) fp32, row (3 ky + kx) 3 + c.
+ *   conv   y = [res2 +] [res1 +] [LeakyReLU 0.2] (conv3x3(x) + b) on v_mfma_f32_16x16x32_f16, one rounding to f16.  x is (F, H, W, Cin);
+ *          with VSP_PARSE_UP the convolution sees its nearest x2, (y >> 1, x >> 1), reflected in the upsampled domain.  The output is
+ *          (F, OH, OW, Cout), OH = (Hd - 1) / stride + 1 over the domain Hd = H or 2 H.  Cin and Cout are multiples of 64.  w_img: the
+ *          f16 image of parse.pack_conv_weight, (Cout / 64, Cin / 64, 18, 4, 64, 8): element j of lane l of block nb of K-step s of
+ *          input chunk kc of output block cb = w[co = 64 cb + 16 nb + (l & 15)][ci = 64 kc + 32 (s & 1) + 8 (l >> 4) + j]
+ *          [ky = (s >> 1) / 3][kx = (s >> 1) % 3].  b: fp32 (Cout).  res1, res2 (or null): f16 tensors of the output's shape; either
+ *          may BE y, no tensor may overlap y otherwise.
+ *   mask   logits = conv3x3(x) + b: 64 -> VSP_PARSE_CLASSES in fp32 (w_img (1, 1, 18, 2, 64, 8), the channels past 19 zero; b padded to
+ *          32); cls = argmax, a tie to the lowest class; keep = keep_table[cls] (a HOST table of 19 bytes, each 0 or 1); logits (or null)
+ *          takes the (F, H, W, 19) fp32 values.  A pixel with a non-finite logit gets class 0 and ORs VSP_PARSE_NONFINITE into info[f]
+ *          (F words, zeroed by the caller).
+ *   blur   m0 = 16384 keep; four 1-D passes (along x, y, x, y) m' = (sum_{k = -R..R} g[|k|] m[reflect101(i + k)] + 2^15) >> 16; out =
+ *          (m + 32) >> 6 in 0 .. 256, the outermost `border` rows and columns 0.  keep (F, S, S) u8, out (F, S, S) u16, work 4 F S S
+ *          bytes.  taps: a HOST table of R + 1 non-negative int32 with g[0] + 2 sum_{k >= 1} g[k] = 65536.
+ * VSP_EINVAL, nothing launched: a null pointer, channel counts that are not served, H or W < 2, a stride other than 1 or 2, up with
+ * stride 2, a buffer off 16-byte alignment, an overlap that is not the aliasing above, taps that do not sum to 65536, R outside
+ * 0 .. min(VSP_PARSE_MAX_RADIUS, S - 1), 2 border > S, a work buffer too small.  VSP_ENOTSUP: a tensor of 2 GiB or more.  F = 0
+ * returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_PARSE_CLASSES 19
+#define VSP_PARSE_MAX_RADIUS 64
+#define VSP_PARSE_NONFINITE 1          /* info bit: a logit of the face was not finite */
+#define VSP_PARSE_ACT 1                /* conv flags */
+#define VSP_PARSE_UP 2
+
+int vsp_parse_head_u8(void* y, const uint8_t* crops, int F, int H, int W, const float* w, const float* b, vsp_stream_t stream);
+int vsp_parse_conv_f16(void* y, const void* x, int F, int H, int W, int Cin, int Cout, int stride, int flags, const void* w_img,
+                       const float* b, const void* res1, const void* res2, vsp_stream_t stream);
+int vsp_parse_mask_u8(uint8_t* cls, uint8_t* keep, float* logits, int32_t* info, const void* x, int F, int H, int W, const void* w_img,
+                      const float* b, const uint8_t* keep_table, vsp_stream_t stream);
+int vsp_parse_blur_u16(uint16_t* out, const uint8_t* keep, uint16_t* work, size_t work_bytes, int F, int S, const int32_t* taps, int R,
+                       int border, vsp_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -227,6 +227,10 @@ SIGNATURES = {
     "vsp_face_crop_aa_u8": [_p, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _i, _p],
     "vsp_face_paste_aa_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p,
                              C.c_size_t, _p, _p, _i, _p],
+    "vsp_face_paste_mask_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p, C.c_size_t, _p, _p, _i, _p,
+                               C.c_size_t, _p],
+    "vsp_face_paste_mask_aa_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _p, _p, _i, _p, _p,
+                                  C.c_size_t, _p, _p, _i, _p, C.c_size_t, _p],
     "vsp_color_fix_u8": [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_size_t, _p, C.c_size_t, _p],
     "vsp_jpeg_intervals": [_i, _i, _i, _i],
     "vsp_jpeg_encode_u8": [_p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p],
@@ -241,6 +245,10 @@ SIGNATURES = {
     "vsp_sr_head_u8": [_p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _p, _p, _p, _p],
     "vsp_sr_body_f16": [_p, _p, C.c_size_t, _p, _p, _i, _p, _p, _p, _p],
     "vsp_sr_tail_u8": [_p, C.c_size_t, _p, _p, _i, _p, C.c_size_t, _p, C.c_size_t, _p, _p, _i, _p, _p, _i, _p],
+    "vsp_parse_head_u8": [_p, _p, _i, _i, _i, _p, _p, _p],
+    "vsp_parse_conv_f16": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
+    "vsp_parse_mask_u8": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p],
+    "vsp_parse_blur_u16": [_p, _p, _p, C.c_size_t, _i, _i, _p, _i, _i, _p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],

@@ -145,6 +145,20 @@ __device__ __forceinline__ void filtered_rgb(const uint8_t* img, int w, int h, i
   v[2] = (int)(((unsigned)acc2 + half) / Wd);
 }
 
+// the paste weight of a face's (S, S) uint16 mask at Q5 crop coordinates, with the four taps and the clamping of bilinear_rgb<true>:
+// (sum of 32 wx wy m + 16384) >> 15 -- a mask of all 256 gives 256.  The result is clamped to 256: weights above it, which
+// vsp_parse_blur_u16 never writes, act as 256 instead of wrapping the blended byte.
+__device__ __forceinline__ int bilinear_mask(const uint16_t* m, int S, int X, int Y) {
+  const int ix = X >> 5, fx = X & 31, iy = Y >> 5, fy = Y & 31;
+  int acc = 16384;
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      acc += 32 * (i ? fx : 32 - fx) * (j ? fy : 32 - fy) * (int)m[(int64_t)min(iy + j, S - 1) * S + min(ix + i, S - 1)];
+  return min(acc >> 15, 256);
+}
+
 // a thread's 4 pixels x 3 channels.  A struct passed by reference: handed to store_crop as a bare array, the non-VEC crop compiled to other code
 struct Quad {
   int v[4][3];
@@ -233,10 +247,12 @@ __global__ __launch_bounds__(kThreads) void face_crop_kernel(uint8_t* out_u8, fl
 }
 
 // grid: (tiles).  One thread owns 4 consecutive pixels of one tile row of the output photo.  fwd: as above.
-template <class Item>
+// MASK (the *_mask entries): face i's ramp weight is scaled by its (S, S) uint16 paste weights at mask + i S S, sampled where
+// the colour is; without it `mask` is not read and the instantiation is the code it was before the parameter existed.
+template <class Item, bool MASK = false>
 __global__ __launch_bounds__(kThreads) void face_paste_kernel(uint8_t* photos, const uint8_t* crops, const int32_t* tables, const Item* items,
                                                                const vsp_face_tile* tiles, const int32_t* tile_faces, const uint16_t* ramp,
-                                                               int L, int S, const int32_t* fwd) {
+                                                               int L, int S, const int32_t* fwd, const uint16_t* mask = nullptr) {
   const vsp_face_tile t = tiles[blockIdx.x];
   const int y = t.y0 + ((int)threadIdx.x >> 3);
   const int xg = t.x0 + ((int)threadIdx.x & 7) * 4;
@@ -258,7 +274,8 @@ __global__ __launch_bounds__(kThreads) void face_paste_kernel(uint8_t* photos, c
   const int none[3] = {0, 0, 0};
   bool touched = false;
   for (int k = 0; k < t.nfaces; ++k) {
-    const Item it = items[tile_faces[t.face0 + k]];
+    const int face = tile_faces[t.face0 + k];
+    const Item it = items[face];
     const int ry = y - it.y0;
     if (ry < 0 || ry >= it.ny) continue;
     const int32_t* ax = tables + it.tab_off;
@@ -272,8 +289,12 @@ __global__ __launch_bounds__(kThreads) void face_paste_kernel(uint8_t* photos, c
       const int X = (cxv + ax[rx]) >> 5, Y = (cyv + bx[rx]) >> 5;
       const int d = min(min(X, Y), min(lim - X, lim - Y));
       if (d < 0) continue;
-      const int w = ramp[min(d >> 2, L - 1)];
+      int w = ramp[min(d >> 2, L - 1)];
       if (w == 0) continue;   // (256 bg + 128) >> 8 = bg
+      if constexpr (MASK) {
+        w = (w * bilinear_mask(mask + (int64_t)face * S * S, S, X, Y) + 128) >> 8;
+        if (w == 0) continue;
+      }
       int f[3];
       if (reach_of(it) == 0)
         bilinear_rgb<true>(crop, S, S, X, Y, none, f);
@@ -451,6 +472,17 @@ int check_paste(const char* what, const uint8_t* photos, size_t photo_bytes, con
   return VSP_OK;
 }
 
+// the one more buffer of the masked paste entries: n faces of S x S uint16 weights on the device
+int check_mask(const char* what, const uint16_t* mask_dev, size_t mask_elems, int n, int S) {
+  if (n == 0) return VSP_OK;
+  VSP_REQUIRE(mask_dev, "%s: null pointer (mask)", what);
+  VSP_REQUIRE(!misaligned(mask_dev, 1u), "%s: misaligned mask", what);
+  VSP_REQUIRE((uint64_t)mask_elems >= (uint64_t)n * (uint64_t)S * (uint64_t)S, "%s: mask of %zu weights, %d faces of %d x %d need more", what,
+              mask_elems, n, S, S);
+  if ((uint64_t)mask_elems * 2ull >= kTwoGiB) return vsp::fail(VSP_ENOTSUP, "%s: a mask of 2 GiB or more", what);
+  return VSP_OK;
+}
+
 // the crop's launch: grid and the choice of the store path
 template <class Item>
 void launch_crop(uint8_t* out_u8, float* out_f32, const uint8_t* src, const int32_t* tables_dev, const Item* items_dev, int n, int S, int border_r,
@@ -510,6 +542,37 @@ int vsp_face_paste_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* cro
   face_paste_kernel<<<dim3((unsigned)ntiles), kThreads, 0, vsp::as_stream(stream)>>>(photos, crops, tables_dev, items_dev, tiles_dev, tile_faces_dev,
                                                                                      ramp_dev, ramp_len, S, fwd_dev);
   return vsp::check_launch("face_paste_aa");
+}
+
+// the two paste entries with a face-parsing mask: the arguments of the entries above, checked by the same validator, and
+// the (n, S, S) uint16 weights
+int vsp_face_paste_mask_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                           const int32_t* tables_dev, size_t table_ints, const vsp_face_item* items, const vsp_face_item* items_dev, int n, int S,
+                           const vsp_face_tile* tiles, const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces,
+                           const int32_t* tile_faces_dev, size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len,
+                           const uint16_t* mask_dev, size_t mask_elems, vsp_stream_t stream) {
+  int rc = check_paste("face_paste_mask", photos, photo_bytes, crops, crop_bytes, tables, tables_dev, table_ints, Fwd{}, items, items_dev, n, S,
+                       tiles, tiles_dev, ntiles, tile_faces, tile_faces_dev, tile_face_ints, ramp, ramp_dev, ramp_len);
+  if (rc == VSP_OK) rc = check_mask("face_paste_mask", mask_dev, mask_elems, n, S);
+  if (rc != VSP_OK || n == 0 || ntiles == 0) return rc;
+  face_paste_kernel<vsp_face_item, true><<<dim3((unsigned)ntiles), kThreads, 0, vsp::as_stream(stream)>>>(
+      photos, crops, tables_dev, items_dev, tiles_dev, tile_faces_dev, ramp_dev, ramp_len, S, nullptr, mask_dev);
+  return vsp::check_launch("face_paste_mask");
+}
+
+int vsp_face_paste_mask_aa_u8(uint8_t* photos, size_t photo_bytes, const uint8_t* crops, size_t crop_bytes, const int32_t* tables,
+                              const int32_t* tables_dev, size_t table_ints, const int32_t* fwd, const int32_t* fwd_dev, size_t fwd_ints,
+                              const vsp_face_aa_item* items, const vsp_face_aa_item* items_dev, int n, int S, const vsp_face_tile* tiles,
+                              const vsp_face_tile* tiles_dev, int ntiles, const int32_t* tile_faces, const int32_t* tile_faces_dev,
+                              size_t tile_face_ints, const uint16_t* ramp, const uint16_t* ramp_dev, int ramp_len, const uint16_t* mask_dev,
+                              size_t mask_elems, vsp_stream_t stream) {
+  int rc = check_paste("face_paste_mask_aa", photos, photo_bytes, crops, crop_bytes, tables, tables_dev, table_ints, Fwd{fwd, fwd_dev, fwd_ints},
+                       items, items_dev, n, S, tiles, tiles_dev, ntiles, tile_faces, tile_faces_dev, tile_face_ints, ramp, ramp_dev, ramp_len);
+  if (rc == VSP_OK) rc = check_mask("face_paste_mask_aa", mask_dev, mask_elems, n, S);
+  if (rc != VSP_OK || n == 0 || ntiles == 0) return rc;
+  face_paste_kernel<vsp_face_aa_item, true><<<dim3((unsigned)ntiles), kThreads, 0, vsp::as_stream(stream)>>>(
+      photos, crops, tables_dev, items_dev, tiles_dev, tile_faces_dev, ramp_dev, ramp_len, S, fwd_dev, mask_dev);
+  return vsp::check_launch("face_paste_mask_aa");
 }
 
 }  // extern "C"

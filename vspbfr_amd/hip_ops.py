@@ -1985,8 +1985,9 @@ def _face_crop(name, plan, items, tables, fwd, src, border, u8, f32):
     return out8, outf
 
 
-def _face_paste(name, plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev):
-    """face_paste_u8 (fwd None: vsp_face_paste_u8 on the plan's paste_items) and face_paste_aa_u8 (vsp_face_paste_aa_u8 on its paste_aa_items)"""
+def _face_paste(name, plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev, mask=None):
+    """face_paste_u8 (fwd None: vsp_face_paste_u8 on the plan's paste_items) and face_paste_aa_u8 (vsp_face_paste_aa_u8 on its paste_aa_items);
+    with `mask`, the (F, S, S) paste weights of parse_blur_u16, the *_mask_* entries of DESIGN 24"""
     import ctypes as Ct
     aa = fwd is not None
     for t, tname in ((photos, "photos"), (crops, "crops"), (items, "items"), (tables, "tables")) + (((fwd, "fwd"),) if aa else ()) + (
@@ -1996,6 +1997,13 @@ def _face_paste(name, plan, photos, crops, items, tables, fwd, tiles, tile_faces
     if not isinstance(ramp_dev, torch.Tensor) or not ramp_dev.is_cuda or ramp_dev.dtype != torch.int16 or ramp_dev.numel() != ramp.size:
         raise RuntimeError(f"{name}: ramp_dev must be the ramp as a CUDA int16 tensor")
     entry, host_items = (lib.vsp_face_paste_aa_u8, plan.paste_aa_items) if aa else (lib.vsp_face_paste_u8, plan.paste_items)
+    mask_args = ()
+    if mask is not None:
+        if (not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype not in (torch.int16, torch.uint16) or not mask.is_contiguous()
+                or mask.numel() != n * S * S):
+            raise RuntimeError(f"{name}: mask must be the ({n}, {S}, {S}) paste weights as a contiguous CUDA 16-bit tensor")
+        entry = lib.vsp_face_paste_mask_aa_u8 if aa else lib.vsp_face_paste_mask_u8
+        mask_args = (_ptr(mask), mask.numel())
     if (photos.numel() != plan.out_bytes or crops.numel() != n * S * S * 3 or items.numel() != Ct.sizeof(host_items._type_) * n
             or tables.numel() != plan.paste_tables.nbytes or (aa and fwd.numel() != plan.paste_fwd.nbytes)
             or tiles.numel() != plan.ntiles * Ct.sizeof(_lib.FaceTile) or tile_faces.numel() != plan.tile_faces.nbytes):
@@ -2003,7 +2011,7 @@ def _face_paste(name, plan, photos, crops, items, tables, fwd, tiles, tile_faces
     check(entry(_ptr(photos), plan.out_bytes, _ptr(crops), crops.numel(), plan.paste_tables.ctypes.data_as(Ct.c_void_p), _ptr(tables),
                 plan.paste_tables.size, *_fwd_args(plan.paste_fwd if aa else None, fwd), Ct.cast(host_items, Ct.c_void_p), _ptr(items), n, S,
                 Ct.cast(plan.tiles, Ct.c_void_p), _ptr(tiles), plan.ntiles, plan.tile_faces.ctypes.data_as(Ct.c_void_p), _ptr(tile_faces),
-                plan.tile_faces.size, ramp.ctypes.data_as(Ct.c_void_p), _ptr(ramp_dev), int(ramp.size), _stream()), name)
+                plan.tile_faces.size, ramp.ctypes.data_as(Ct.c_void_p), _ptr(ramp_dev), int(ramp.size), *mask_args, _stream()), name)
     return photos
 
 
@@ -2031,6 +2039,17 @@ def face_paste_aa_u8(plan, photos, crops, items, tables, fwd, tiles, tile_faces,
     """face_paste_u8 for a FacePlan built with antialias=True (vsp_face_paste_aa_u8): `items` is the plan's paste_aa_items section and
     `fwd` its paste_fwd section.  Returns photos."""
     return _face_paste("face_paste_aa_u8", plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev)
+
+
+def face_paste_mask_u8(plan, photos, crops, items, tables, tiles, tile_faces, ramp, ramp_dev, mask):
+    """face_paste_u8 through a face-parsing mask (vsp_face_paste_mask_u8): mask is the (F, S, S) tensor of parse_blur_u16, paste
+    weights 0 .. 256 sampled with the colour's four taps; the blend weight is (ramp * wm + 128) >> 8.  Returns photos."""
+    return _face_paste("face_paste_mask_u8", plan, photos, crops, items, tables, None, tiles, tile_faces, ramp, ramp_dev, mask)
+
+
+def face_paste_mask_aa_u8(plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev, mask):
+    """face_paste_aa_u8 through a face-parsing mask (vsp_face_paste_mask_aa_u8): the colour keeps its tent filter, the mask its four taps"""
+    return _face_paste("face_paste_mask_aa_u8", plan, photos, crops, items, tables, fwd, tiles, tile_faces, ramp, ramp_dev, mask)
 
 
 COLOR_FIX_MODES = {"stats": 0, "wavelet": 1}      # include/vspbfr_hip.h VSP_COLOR_FIX_STATS / VSP_COLOR_FIX_WAVELET
@@ -2237,10 +2256,114 @@ def sr_tail_u8(out, info, x, src, items, items_dev, n, w_img, b, scale, out_f32=
     return out
 
 
+# ------------------------------------------------------------------------------------------------- face parsing
+PARSE_CLASSES, PARSE_MAX_RADIUS, PARSE_NONFINITE = 19, 64, 1      # include/vspbfr_hip.h VSP_PARSE_*
+PARSE_ACT, PARSE_UP = 1, 2
+PARSE_KEEP = tuple(0 if c in (0, 14, 16, 17, 18) else 1 for c in range(19))     # the common MASK_COLORMAP: background, neck, clothes, hair, hat go
+
+
+def _parse_t(t, name, dtype, numel=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise RuntimeError(f"{name} must be a contiguous CUDA {dtype} tensor" + (f" of {numel} elements" if numel is not None else ""))
+    return t
+
+
+def parse_conv_out(H, W, stride=1, up=False):
+    """the output map of parse_conv_f16 for an (H, W) input"""
+    hd, wd = (2 * H, 2 * W) if up else (H, W)
+    return ((hd - 1) // 2 + 1, (wd - 1) // 2 + 1) if stride == 2 else (hd, wd)
+
+
+def parse_head_u8(y, crops, w, b):
+    """ParseNet's first layer (vsp_parse_head_u8): crops (F, H, W, 3) uint8 -> y, a float16 tensor of F H W 64 elements, = conv3x3 of
+    (crops / 255 - 0.5) / 0.5 behind a reflection padding, + b, without an activation.  w (27, 64), b (64) float32.  Returns y."""
+    _u8(crops, "crops"), _req(w, "w"), _req(b, "b")
+    if crops.dim() != 4 or crops.shape[3] != 3 or w.numel() != 27 * 64 or b.numel() != 64:
+        raise RuntimeError(f"parse_head_u8: crops {tuple(crops.shape)}, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    F, H, W = (int(v) for v in crops.shape[:3])
+    _parse_t(y, "y", torch.float16, F * H * W * 64)
+    check(lib.vsp_parse_head_u8(_ptr(y), _ptr(crops), F, H, W, _ptr(w), _ptr(b), _stream()), "parse_head_u8")
+    return y
+
+
+def parse_conv_f16(y, x, F, H, W, w_img, b, stride=1, act=False, up=False, res1=None, res2=None):
+    """One 3x3 convolution of ParseNet (vsp_parse_conv_f16): x holds (F, H, W, Cin) float16, y takes (F, OH, OW, Cout) with (OH, OW) =
+    parse_conv_out(H, W, stride, up); reflection padding, optional fused nearest x2 (`up`), LeakyReLU(0.2) (`act`) and up to two float16
+    residuals of y's shape, either of which may be y itself.  w_img: parse.pack_conv_weight's image (Cout / 64, Cin / 64, 18, 4, 64, 8)
+    float16; b float32 (Cout).  Returns y."""
+    _parse_t(w_img, "w_img", torch.float16), _req(b, "b")
+    if w_img.dim() != 6 or tuple(w_img.shape[2:]) != (18, 4, 64, 8):
+        raise RuntimeError(f"parse_conv_f16: w_img {tuple(w_img.shape)}, expected (Cout / 64, Cin / 64, 18, 4, 64, 8)")
+    cout, cin = 64 * int(w_img.shape[0]), 64 * int(w_img.shape[1])
+    F, H, W = int(F), int(H), int(W)
+    oh, ow = parse_conv_out(H, W, stride, up)
+    if b.numel() != cout:
+        raise RuntimeError(f"parse_conv_f16: {b.numel()} biases for {cout} channels")
+    _parse_t(x, "x", torch.float16, F * H * W * cin), _parse_t(y, "y", torch.float16, F * oh * ow * cout)
+    for r, name in ((res1, "res1"), (res2, "res2")):
+        if r is not None:
+            _parse_t(r, name, torch.float16, y.numel())
+    check(lib.vsp_parse_conv_f16(_ptr(y), _ptr(x), F, H, W, cin, cout, int(stride), (PARSE_ACT if act else 0) | (PARSE_UP if up else 0),
+                                 _ptr(w_img), _ptr(b), _ptr(res1), _ptr(res2), _stream()), "parse_conv_f16")
+    return y
+
+
+def parse_mask_u8(x, F, H, W, w_img, b, keep=PARSE_KEEP, info=None, logits=False, out=None):
+    """ParseNet's out_mask_conv and what follows it (vsp_parse_mask_u8): x (F, H, W, 64) float16 -> (classes (F, H, W) uint8 = argmax of the
+    19 fp32 logits, a tie to the lowest class; keep map (F, H, W) uint8 = keep[class]; info (F) int32 with PARSE_NONFINITE for a face
+    that had a non-finite logit -- its pixel gets class 0; the (F, H, W, 19) fp32 logits or None).  w_img (1, 1, 18, 2, 64, 8) float16,
+    b float32 (32, the last 13 zero); keep: 19 values 0 / 1 on the host.  logits: False, True (a new tensor) or a contiguous float32
+    tensor of F H W 19 elements to write into; out: None or (classes, keep map), contiguous uint8 tensors of F H W elements to write into."""
+    import ctypes as Ct
+    F, H, W = int(F), int(H), int(W)
+    _parse_t(x, "x", torch.float16, F * H * W * 64), _parse_t(w_img, "w_img", torch.float16, 18 * 2 * 64 * 8), _req(b, "b")
+    keep = [int(v) for v in keep]
+    if b.numel() != 32 or len(keep) != PARSE_CLASSES or any(v not in (0, 1) for v in keep):
+        raise RuntimeError("parse_mask_u8: b of 32 values (19 and padding), keep of 19 values 0 / 1")
+    if info is None:
+        info = torch.zeros(F, dtype=torch.int32, device=x.device)
+    _parse_t(info, "info", torch.int32, F)
+    if out is None:
+        out = (torch.empty((F, H, W), dtype=torch.uint8, device=x.device), torch.empty((F, H, W), dtype=torch.uint8, device=x.device))
+    cls, kmap = out
+    _parse_t(cls, "classes", torch.uint8, F * H * W), _parse_t(kmap, "keep map", torch.uint8, F * H * W)
+    if isinstance(logits, torch.Tensor):
+        lg = _parse_t(logits, "logits", torch.float32, F * H * W * PARSE_CLASSES)
+    else:
+        lg = torch.empty((F, H, W, PARSE_CLASSES), dtype=torch.float32, device=x.device) if logits else None
+    table = (Ct.c_uint8 * PARSE_CLASSES)(*keep)
+    check(lib.vsp_parse_mask_u8(_ptr(cls), _ptr(kmap), _ptr(lg), _ptr(info), _ptr(x), F, H, W, _ptr(w_img), _ptr(b),
+                                Ct.cast(table, Ct.c_void_p), _stream()), "parse_mask_u8")
+    return cls, kmap, info, lg
+
+
+def parse_blur_u16(keep, taps, border, out=None, work=None):
+    """The paste weights of a keep map (vsp_parse_blur_u16): keep (F, S, S) uint8 -> (F, S, S) torch.uint16 in 0 .. 256 -- m0 = 16384 keep,
+    four 1-D integer passes with reflect-101 borders (x, y, x, y), (m + 32) >> 6, the outermost `border` rows and columns 0.  taps: R + 1 non-negative ints on the host, g[0] + 2 sum g[k >= 1]
+    = 65536.  work: a uint16 tensor of 2 F S S elements or None (allocated here)."""
+    import ctypes as Ct
+    _u8(keep, "keep")
+    if keep.dim() != 3 or keep.shape[1] != keep.shape[2]:
+        raise RuntimeError(f"parse_blur_u16: keep {tuple(keep.shape)}, expected (F, S, S)")
+    F, S = int(keep.shape[0]), int(keep.shape[1])
+    taps = [int(v) for v in taps]
+    if not taps or len(taps) > PARSE_MAX_RADIUS + 1:
+        raise RuntimeError(f"parse_blur_u16: {len(taps)} taps (1..{PARSE_MAX_RADIUS + 1})")
+    if out is None:
+        out = torch.empty((F, S, S), dtype=torch.uint16, device=keep.device)
+    if work is None:
+        work = torch.empty(2 * F * S * S, dtype=torch.uint16, device=keep.device)
+    _parse_t(out, "out", torch.uint16, F * S * S), _parse_t(work, "work", torch.uint16)
+    table = (Ct.c_int32 * len(taps))(*taps)
+    check(lib.vsp_parse_blur_u16(_ptr(out), _ptr(keep), _ptr(work), work.numel() * 2, F, S, Ct.cast(table, Ct.c_void_p), len(taps) - 1, int(border),
+                                 _stream()), "parse_blur_u16")
+    return out
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types
-    skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check"}
+    skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check", "parse_conv_out"}
     g = globals()
     for name, obj in list(g.items()):
         if isinstance(obj, types.FunctionType) and not name.startswith("_") and name not in skip and obj.__module__ == __name__:

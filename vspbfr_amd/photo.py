@@ -414,10 +414,11 @@ def crop_faces(plan, device, u8=True, f32=False, border=DEFAULT_BORDER):
     return hip_ops.face_crop_u8(plan, dev["crop_items"], dev["crop_tables"], dev["photos"], border=border, u8=u8, f32=f32)
 
 
-def paste_faces(plan, restored_u8, device, ramp=None, out=None):
+def paste_faces(plan, restored_u8, device, ramp=None, out=None, mask=None):
     """Paste the restored crops ((F, S, S, 3) uint8 on the device) into the output photos, in place on `out` (a packed device buffer of
     plan.out_bytes; default plan.background(device)) -> out.  ramp: uint16 weights 0..256 over the distance from the crop border in
-    1/8 px, ramp[0] = 0; default default_ramp().  plan.split(out) gives the photos."""
+    1/8 px, ramp[0] = 0; default default_ramp().  plan.split(out) gives the photos.  mask: the (F, S, S) uint16 paste weights
+    of parse.FaceParser.mask on the device -- the ramp weight is scaled by the mask sampled where the colour is; None: the unmasked entries."""
     import torch
 
     from . import hip_ops
@@ -431,7 +432,13 @@ def paste_faces(plan, restored_u8, device, ramp=None, out=None):
     ramp_dev = plan._ramps.get(key)              # a plan pasted more than once uploads its ramp once
     if ramp_dev is None:
         ramp_dev = plan._ramps[key] = torch.from_numpy(ramp.view(np.int16).copy()).to(device)
-    if plan.antialias:
+    if mask is not None and plan.antialias:
+        hip_ops.face_paste_mask_aa_u8(plan, out, restored_u8, dev["paste_aa_items"], dev["paste_tables"], dev["paste_fwd"], dev["tiles"],
+                                      dev["tile_faces"], ramp, ramp_dev, mask)
+    elif mask is not None:
+        hip_ops.face_paste_mask_u8(plan, out, restored_u8, dev["paste_items"], dev["paste_tables"], dev["tiles"], dev["tile_faces"], ramp,
+                                   ramp_dev, mask)
+    elif plan.antialias:
         hip_ops.face_paste_aa_u8(plan, out, restored_u8, dev["paste_aa_items"], dev["paste_tables"], dev["paste_fwd"], dev["tiles"],
                                  dev["tile_faces"], ramp, ramp_dev)
     else:
@@ -475,10 +482,14 @@ class PhotoRestorer:
     (vsp_quantize_u8_nhwc), paste (vsp_face_paste_u8) onto the photos -- resized first by Pillow's LANCZOS for upscale 2 or 4.
     antialias=True: the anti-aliased entries for crop and paste.  color_fix="stats" or "wavelet": the restored crops take
     their colours back from the crops (vsp_color_fix_u8) and the fixed crops are pasted.  background: an upscale.SrUpscaler
-    whose output replaces the LANCZOS resize under the faces (upscale 2 or 4, at most the network's scale)."""
+    whose output replaces the LANCZOS resize under the faces (upscale 2 or 4, at most the network's scale).  parser: a
+    parse.FaceParser -- the paste goes through the mask it computes from the network's `restored` crops (also when a colour
+    fix is on; the crops that are pasted stay what they are); parse_taps / parse_border / parse_keep are handed to its mask().  After a
+    call `parse_info` holds {"classes", "mask", "flags"} of the call's faces (None without a parser)."""
 
     def __init__(self, pipe, batch, upscale=1, size=512, inset=DEFAULT_INSET, feather=DEFAULT_FEATHER, border=DEFAULT_BORDER,
-                 antialias=False, color_fix=None, color_levels=5, background=None):
+                 antialias=False, color_fix=None, color_levels=5, background=None, parser=None, parse_taps=None, parse_border=None,
+                 parse_keep=None):
         if int(upscale) not in (1, 2, 4) or int(batch) < 1:
             raise ValueError(f"PhotoRestorer: batch {batch}, upscale {upscale}")
         if background is not None and (int(upscale) == 1 or background.scale < int(upscale)):
@@ -488,6 +499,19 @@ class PhotoRestorer:
         self.antialias = bool(antialias)       # minified faces through the tent filter of DESIGN 16, crop and paste
         self.ramp = default_ramp(inset, feather)
         self.color_fix, self.color_levels = check_color_fix(color_fix, color_levels)
+        if parser is not None:
+            from .parse import check_size
+            check_size(int(size))
+        self.parser, self.parse_taps, self.parse_border, self.parse_keep, self.parse_info = parser, parse_taps, parse_border, parse_keep, None
+
+    def _mask(self, restored):
+        """the paste weights of the restored crops, or None without a parser"""
+        self.parse_info = None
+        if self.parser is None or restored.shape[0] == 0:
+            return None
+        mask, flags, classes = self.parser.mask(restored, taps=self.parse_taps, border=self.parse_border, keep=self.parse_keep, classes=True)
+        self.parse_info = {"classes": classes, "mask": mask, "flags": flags}
+        return mask
 
     def __call__(self, photos, landmarks, device, names=None, device_photos=None):
         """photos: uint8 (h, w, 3) arrays -- or their (h, w) with device_photos, the packed device buffer that holds them back to back
@@ -501,6 +525,7 @@ class PhotoRestorer:
         faces = [(k, pts) for k, per in enumerate(landmarks) for pts in (per or [])]
         plan = FacePlan(photos, faces, self.size, self.upscale, names, antialias=self.antialias, device_photos=device_photos)
         S = self.size
+        self.parse_info = None
         if plan.n == 0:
             empty = torch.empty((0, S, S, 3), dtype=torch.uint8, device=device)
             plan.out_packed = plan.background(device) if self.background is None else plan.background(device, self.background)
@@ -514,9 +539,10 @@ class PhotoRestorer:
                 restored.append(hip_ops.quantize_u8_nhwc(out["restored"].contiguous(), -1.0, 1.0))
         restored = torch.cat(restored) if len(restored) > 1 else restored[0]
         bg = None if self.background is None else plan.background(device, self.background)
+        mask = self._mask(restored)
         if self.color_fix is None:
-            out = plan.out_packed = paste_faces(plan, restored, device, self.ramp, out=bg)
+            out = plan.out_packed = paste_faces(plan, restored, device, self.ramp, out=bg, mask=mask)
             return plan.split(out), crops, restored, plan
         fixed = color_fix(crops, restored, self.color_fix, plan, device, self.color_levels)
-        out = plan.out_packed = paste_faces(plan, fixed, device, self.ramp, out=bg)
+        out = plan.out_packed = paste_faces(plan, fixed, device, self.ramp, out=bg, mask=mask)
         return plan.split(out), crops, restored, plan, fixed

@@ -4,7 +4,7 @@
         [--save_faces] [--inset PX] [--feather PX] [--antialias] [--color_fix {none,stats,wavelet}] [--color_levels L]
         [--detect_threshold 0.8] [--detect_nms 0.4] [--detect_side 1024] [--detect_max_faces N] [--detect_min_face PX]
         [--format {png,jpg}] [--quality Q] [--subsampling {420,444}] [--encode {host,device}] [--decode {host,device}]
-        [--png_encode {host,device}] [--bg_weights W [--bg_band_rows N]] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
+        [--png_encode {host,device}] [--bg_weights W [--bg_band_rows N]] [--parse_weights W [--parse_sigma F] [--parse_border PX]] <the model flags of vspbfr_amd.restoration_test: --ckpt --ddpm_ckpt --psp_checkpoint_path --size
         --mixing --channel_multiplier --timesteps --no_sample --conv_dtype --batch>
 
 `vspbfr_amd.restoration_test` takes aligned 512 x 512 faces; this CLI takes photos of any size with any number of faces.  Exactly one of
@@ -61,6 +61,15 @@ expects is unverified against a real file.  A x4 network at --upscale 2 goes thr
 a x2 network at --upscale 4 is refused.  --bg_band_rows N processes every photo in bands of N rows (the same bytes).  report.json then
 lists `background` = {model, num_conv, scale, banded, nonfinite}; `nonfinite` names the photos in which a value was not finite before the
 clamp (written as 0): a warning, not an abort.  Without the flag nothing changes.
+
+--parse_weights W: the paste goes through a face-parsing mask (vspbfr_amd.parse, csrc/parse.hip): facexlib's ParseNet from the
+checkpoint W runs on the network's restored crop, the face classes are kept (everything but background, neck, clothes, hair and hat), the
+binary map is blurred twice (--parse_sigma F, default 11 size / 512) and its outermost --parse_border PX rows and columns (default
+round(10 size / 512)) are set to 0; the blend weight is the feather ramp times that mask.  No weights are shipped, and the key layout the
+loader expects is unverified against a real file.  With --save_faces also <stem>_<k>_mask.png (grey, (weight 255 + 128) >> 8) and
+<stem>_<k>_parse.png (class indices).  report.json then lists `parse` = {model, sigma, radius, border, nonfinite} and per photo
+`mask_mean`, one value per face; `nonfinite` names the photos with a face that had a non-finite logit (those pixels keep the photo): a
+warning, not an abort.  Without the flag nothing changes.
 
 Multi-GPU as the other CLIs: `python -m torch.distributed.run --nproc-per-node N -m vspbfr_amd.restore_photos ...`; every rank takes a
 contiguous shard of the sorted photo list, no collective."""
@@ -161,6 +170,7 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
     ragged = png_device and not jpg          # a group's photos go through one call of the ragged PNG encoder
     report, found = [], {}
     bg_banded, bg_nonfinite = False, []
+    parser, parse_nonfinite = getattr(restorer, "parser", None), []
     if detector is not None:
         landmarks = {}
     print("restoring photos: %d (rank %d handles %d..%d)" % (len(names), rank, lo, hi))
@@ -183,6 +193,14 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
             info = plan.background_info
             bg_banded = bg_banded or any(info["banded"])
             bg_nonfinite += [n for n, f in zip(group, info["flags"].cpu().tolist()) if f]
+        pinfo = restorer.parse_info if parser is not None else None
+        if pinfo is not None:
+            from .parse import mask_png
+            mask_mean = (pinfo["mask"].view(torch.int16).to(torch.float32).mean(dim=(1, 2)) / 256).cpu().tolist()
+            parse_flags = pinfo["flags"].cpu().tolist()
+            if args.save_faces:
+                from PIL import Image
+                mask_grey, parse_cls = mask_png(pinfo["mask"]).cpu().numpy(), pinfo["classes"].cpu().numpy()
         stems = [os.path.join(args.out, os.path.splitext(n)[0]) for n in group]
         for stem in stems:
             os.makedirs(os.path.dirname(stem) or ".", exist_ok=True)
@@ -199,6 +217,9 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
                     writer.submit(restored[i:i + 1], [f"{stem}_{j}_restore.png"])
                     if fixed:
                         writer.submit(fixed[0][i:i + 1], [f"{stem}_{j}_fixed.png"])
+                    if pinfo is not None:       # two small single-channel files per face: the RGB writers do not take them
+                        Image.fromarray(mask_grey[i]).save(f"{stem}_{j}_mask.png")
+                        Image.fromarray(parse_cls[i]).save(f"{stem}_{j}_parse.png")
             report.append({"photo": n, "faces": len(mine), "output": os.path.relpath(stem + ext, args.out),
                            "size": [int(outs[k].shape[1]), int(outs[k].shape[0])]})
             if decode is not None:
@@ -209,6 +230,10 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
                     report[-1]["dropped"] = found[n]["dropped"]
                 if found[n]["status"]:
                     report[-1]["detect_status"] = found[n]["status"]
+            if pinfo is not None:
+                report[-1]["mask_mean"] = [round(mask_mean[i], 6) for i in mine]
+                if any(parse_flags[i] for i in mine):
+                    parse_nonfinite.append(n)
             if plan.antialias:
                 report[-1]["crop_minify"] = [round(plan.crop_minify[i], 6) for i in mine]
                 report[-1]["paste_minify"] = [round(plan.paste_minify[i], 6) for i in mine]
@@ -226,6 +251,11 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
         head.update(background=restorer.background.describe(bg_banded, bg_nonfinite))
         if bg_nonfinite:
             print("warning: non-finite background values were written as 0 in: " + ", ".join(bg_nonfinite))
+    if parser is not None:
+        head.update(parse=parser.describe(args.size, sigma=getattr(args, "parse_sigma", None), border=restorer.parse_border,
+                                          nonfinite=parse_nonfinite))
+        if parse_nonfinite:
+            print("warning: non-finite parsing logits (those pixels are class 0 and keep the photo) in: " + ", ".join(parse_nonfinite))
     if detector is not None:
         from .detect import write_landmarks
         head.update(detect=detect_params)
@@ -278,7 +308,18 @@ def main(argv=None):
     ap.add_argument("--bg_weights", type=str, default=None,
                     help="SRVGGNetCompact checkpoint (not shipped): upscale the photo under the faces with it instead of LANCZOS; needs --upscale 2 or 4")
     ap.add_argument("--bg_band_rows", type=int, default=None, help="--bg_weights: process every photo in bands of this many rows (the same bytes)")
+    ap.add_argument("--parse_weights", type=str, default=None,
+                    help="ParseNet checkpoint (not shipped): paste through the face-parsing mask of the restored crop instead of the whole square")
+    ap.add_argument("--parse_sigma", type=float, default=None, help="--parse_weights: sigma of the mask's two Gaussian blurs (default 11 size / 512; the blur's radius is round(50 size / 512) "
+                         "but at most 64, so above --size 655 the taps are cut below 3 sigma)")
+    ap.add_argument("--parse_border", type=int, default=None, help="--parse_weights: px at each side of the mask set to 0 (default round(10 size / 512))")
     args = ap.parse_args(argv)
+    parse_state = None
+    if args.parse_weights is not None:
+        from .parse import check_parse_arguments
+        parse_state, parse_taps, parse_border = check_parse_arguments(ap, args.parse_weights, args.size, args.parse_sigma, args.parse_border)
+    elif args.parse_sigma is not None or args.parse_border is not None:
+        ap.error("--parse_sigma and --parse_border belong to --parse_weights")
     bg_state = None
     if args.bg_weights is not None:
         from .upscale import check_background_arguments
@@ -338,6 +379,9 @@ def main(argv=None):
     if bg_state is not None:
         from .upscale import SrUpscaler
         restorer.background = SrUpscaler(bg_state, device, band_rows=args.bg_band_rows)
+    if parse_state is not None:
+        from .parse import FaceParser
+        restorer.parser, restorer.parse_taps, restorer.parse_border = FaceParser(parse_state, device), parse_taps, parse_border
     detector = None
     if args.detect_weights is not None:
         try:
