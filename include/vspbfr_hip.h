@@ -629,10 +629,14 @@ int vsp_color_affine_f32(float* y, const float* x, const float* M, const float* 
  * Operators of the training losses (BASELINE configs[4]: LPIPS-VGG + ArcFace identity; reference restoration_train.py:236-245).
  *   vsp_maxpool2d_f32 / _bwd   F.max_pool2d(x, k, s, p) in floor mode on `planes` = B*C planes (torchvision 0.13 vgg16.features
  *                              2x2/2, resnet101 3x3/2 pad 1); the backward recomputes each window's arg-max (first maximum in
- *                              row-major order, ATen's rule) from x; dx is overwritten
+ *                              row-major order, the LAST NaN if there is one: ATen's rule) from x; dx is overwritten
  *   vsp_lpips_layer_f32        out[b] = mean_p sum_c w[c] (f0/(|f0|_c + 1e-10) - f1/(|f1|_c + 1e-10))^2  -- normalize_tensor,
  *                              squared difference, the 1x1 `lin` layer and spatial_average of one LPIPS level in one stream
  *                              (my_lpips/networks_basic.py:73-83, my_lpips/__init__.py:44-46); f0, f1 (B,C,HW), w (C), out (B)
+ *   vsp_lpips_layer_ws_f32     the same with a caller's work buffer (contents irrelevant before, undefined after): every workgroup stores
+ *                              its sum there and one more launch adds them in a fixed order -- the same bits in every run.  The form
+ *                              without it adds one atomic per workgroup onto out[b]: up to 2048 serial float additions, an error of up
+ *                              to 2e-6 of the result at the widest grid, in an order that changes from run to run
  *   vsp_lpips_layer_bwd_f32    df1 = gout[b] * d out[b] / d f1   (the reference calls forward(target, pred): my_lpips/__init__.py:42)
  *   vsp_resize_bilinear_bwd_f32  adjoint of vsp_resize_bilinear_f32 (F.interpolate(size=112) in Loss/id_loss.py:37-41); dx overwritten
  * ---------------------------------------------------------------------------------------------- */
@@ -641,6 +645,9 @@ int vsp_maxpool2d_f32(float* out, const float* x, int64_t planes, int H, int W, 
 int vsp_maxpool2d_bwd_f32(float* dx, const float* dy, const float* x, int64_t planes, int H, int W, int OH, int OW, int k, int s,
                           int p, vsp_stream_t stream);
 int vsp_lpips_layer_f32(float* out, const float* f0, const float* f1, const float* w, int B, int C, int HW, vsp_stream_t stream);
+#define VSP_LPIPS_WORK_BLOCKS 2048   /* the widest grid per sample: work of B * VSP_LPIPS_WORK_BLOCKS floats always suffices */
+int vsp_lpips_layer_ws_f32(float* out, float* work, int64_t work_floats, const float* f0, const float* f1, const float* w, int B, int C, int HW,
+                           vsp_stream_t stream);
 int vsp_lpips_layer_bwd_f32(float* df1, const float* f0, const float* f1, const float* w, const float* gout, int B, int C, int HW,
                             vsp_stream_t stream);
 int vsp_resize_bilinear_bwd_f32(float* dx, const float* dy, int64_t planes, int IH, int IW, int OH, int OW, vsp_stream_t stream);

@@ -186,6 +186,7 @@ SIGNATURES = {
     "vsp_maxpool2d_f32": [_p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
     "vsp_maxpool2d_bwd_f32": [_p, _p, _p, _i64, _i, _i, _i, _i, _i, _i, _i, _p],
     "vsp_lpips_layer_f32": [_p, _p, _p, _p, _i, _i, _i, _p],
+    "vsp_lpips_layer_ws_f32": [_p, _p, _i64, _p, _p, _p, _i, _i, _i, _p],
     "vsp_lpips_layer_bwd_f32": [_p, _p, _p, _p, _p, _i, _i, _i, _p],
     "vsp_resize_bilinear_bwd_f32": [_p, _p, _i64, _i, _i, _i, _i, _p],
     "vsp_conv2d_wgrad_f32": [C.POINTER(ConvWgradParams), _p],

@@ -22,7 +22,8 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
-// arg-max of the window of output (oy, ox): first maximum in scan order (NaN wins, as in ATen's max_pool2d_with_indices)
+// arg-max of the window of output (oy, ox): first maximum in scan order; a NaN replaces whatever the running maximum is (ATen's
+// max_pool2d_with_indices tests `val > maxval || isnan(val)`), so the LAST NaN of a window takes the gradient
 __device__ __forceinline__ int window_argmax(const float* xp, int H, int W, int oy, int ox, int k, int s, int p, float* vmax) {
   int y0 = oy * s - p, x0 = ox * s - p;
   const int y1 = min(y0 + k, H), x1 = min(x0 + k, W);
@@ -33,7 +34,7 @@ __device__ __forceinline__ int window_argmax(const float* xp, int H, int W, int 
   for (int y = y0; y < y1; ++y)
     for (int x = x0; x < x1; ++x) {
       const float v = xp[y * W + x];
-      if (v > m || (v != v && m == m)) {
+      if (v > m || v != v) {
         m = v;
         best = y * W + x;
       }
@@ -81,8 +82,11 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(float* __restrict__ dx
   }
 }
 
-// ---- LPIPS layer distance.  grid (blocks over pixels, B); out[b] += (1/HW) * sum over the block's pixels
-__global__ __launch_bounds__(256) void lpips_layer_fwd_kernel(float* __restrict__ out, const float* __restrict__ f0,
+// ---- LPIPS layer distance.  grid (blocks over pixels, B).  With `part` (gridDim.x floats per sample) a block stores the sum over its pixels
+//      and lpips_finish_kernel adds them in a fixed order; without, out[b] += (1/HW) * that sum through one atomic per block -- up to 2048
+//      serial float additions onto one running sum, whose error grows with the square root of the grid (measured against float64 at 2048
+//      blocks: a standard deviation of 0.7e-6 of the result over inputs, 2e-6 reached) and changes from run to run.
+__global__ __launch_bounds__(256) void lpips_layer_fwd_kernel(float* __restrict__ out, float* __restrict__ part, const float* __restrict__ f0,
                                                                const float* __restrict__ f1, const float* __restrict__ w, int C,
                                                                int HW, float eps) {
   const int b = blockIdx.y;
@@ -108,7 +112,24 @@ __global__ __launch_bounds__(256) void lpips_layer_fwd_kernel(float* __restrict_
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) unsafeAtomicAdd(out + b, (red[0] + red[1] + red[2] + red[3]) / (float)HW);
+  if (threadIdx.x == 0) {
+    const float s = red[0] + red[1] + red[2] + red[3];
+    if (part) part[(int64_t)b * gridDim.x + blockIdx.x] = s;
+    else unsafeAtomicAdd(out + b, s / (float)HW);
+  }
+}
+
+// out[b] = (1/HW) * sum of the sample's nblk block sums: one workgroup per sample, thread t adds blocks t, t + 256, ... in turn, then the
+// butterfly and the four wave sums -- the same order in every run
+__global__ __launch_bounds__(256) void lpips_finish_kernel(float* __restrict__ out, const float* __restrict__ part, int nblk, int HW) {
+  const float* pp = part + (int64_t)blockIdx.x * nblk;
+  float acc = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += 256) acc += pp[i];
+  __shared__ float red[4];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) out[blockIdx.x] = (red[0] + red[1] + red[2] + red[3]) / (float)HW;
 }
 
 // d out[b] / d f1:  with n = |f1|, r = 1/(n+eps), e_c = f0_c r0 - f1_c r,  g_c = -2 w_c e_c:
@@ -156,8 +177,9 @@ __device__ __forceinline__ float part_sum(float v) {
   return v;
 }
 template <int LPP, bool BWD>
-__global__ __launch_bounds__(256) void lpips_layer_reg_kernel(float* __restrict__ outp, const float* __restrict__ f0, const float* __restrict__ f1,
-                                                               const float* __restrict__ w, const float* __restrict__ gout, int HW, float eps) {
+__global__ __launch_bounds__(256) void lpips_layer_reg_kernel(float* __restrict__ outp, float* __restrict__ bsum, const float* __restrict__ f0,
+                                                               const float* __restrict__ f1, const float* __restrict__ w,
+                                                               const float* __restrict__ gout, int HW, float eps) {
   constexpr int PXW = 64 / LPP;                       // pixels per wave
   const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int part = lane / PXW, pl = lane % PXW;
@@ -219,7 +241,11 @@ __global__ __launch_bounds__(256) void lpips_layer_reg_kernel(float* __restrict_
     acc = wave_sum(acc);   // (all parts: every lane holds its share of the channels)
     if (lane == 0) red[wave] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(outp + b, (red[0] + red[1] + red[2] + red[3]) / (float)HW);
+    if (threadIdx.x == 0) {   // (forward only: as in lpips_layer_fwd_kernel)
+      const float s = red[0] + red[1] + red[2] + red[3];
+      if (bsum) bsum[(int64_t)b * gridDim.x + blockIdx.x] = s;
+      else unsafeAtomicAdd(outp + b, s / (float)HW);
+    }
   }
 }
 
@@ -258,16 +284,16 @@ extern "C" {
 
 // 2 x 2 windows at stride 2 without padding on planes whose width is a multiple of 4 (every pooling of the LPIPS VGG): a thread owns two
 // neighbouring windows = four columns of two input rows -- 16-byte loads / stores, no index arithmetic per element, the same
-// first-maximum-in-scan-order rule as window_argmax (the generic gather form ran the 64-channel 512^2 level at 1.9 TB/s).
-__device__ __forceinline__ int argmax4(float a, float b, float c, float d) {   // scan order (y0,x0) (y0,x1) (y1,x0) (y1,x1); NaN wins
+// first-maximum / last-NaN rule as window_argmax (the generic gather form ran the 64-channel 512^2 level at 1.9 TB/s).
+__device__ __forceinline__ int argmax4(float a, float b, float c, float d) {   // scan order (y0,x0) (y0,x1) (y1,x0) (y1,x1); the last NaN wins
   int best = 0;
   float m = a;
-  if (b > m || (b != b && m == m)) { m = b; best = 1; }
-  if (c > m || (c != c && m == m)) { m = c; best = 2; }
-  if (d > m || (d != d && m == m)) { m = d; best = 3; }
+  if (b > m || b != b) { m = b; best = 1; }
+  if (c > m || c != c) { m = c; best = 2; }
+  if (d > m || d != d) { m = d; best = 3; }
   return best;
 }
-__device__ __forceinline__ float max4(float a, float b, float c, float d) {
+__device__ __forceinline__ float max4(float a, float b, float c, float d) {   // (the value is NaN whichever NaN is kept)
   float m = a;
   if (b > m || (b != b && m == m)) m = b;
   if (c > m || (c != c && m == m)) m = c;
@@ -337,25 +363,36 @@ int vsp_maxpool2d_bwd_f32(float* dx, const float* dy, const float* x, int64_t pl
   return vsp::check_launch("maxpool2d_bwd");
 }
 
-int vsp_lpips_layer_f32(float* out, const float* f0, const float* f1, const float* w, int B, int C, int HW, vsp_stream_t stream) {
-  VSP_REQUIRE(B >= 0 && C >= 1 && HW >= 1, "lpips_layer: bad dims");
+// `work` null: the atomic form (out is cleared first); else B * grid floats of block sums and lpips_finish_kernel
+static int lpips_forward(const char* what, float* out, float* work, int64_t work_floats, const float* f0, const float* f1, const float* w, int B, int C,
+                         int HW, vsp_stream_t stream) {
+  VSP_REQUIRE(B >= 0 && C >= 1 && HW >= 1, "%s: bad dims", what);
   if (B == 0) return VSP_OK;
-  VSP_REQUIRE(out && f0 && f1 && w, "lpips_layer: null pointer");
+  VSP_REQUIRE(out && f0 && f1 && w, "%s: null pointer", what);
   hipStream_t st = vsp::as_stream(stream);
-  if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return vsp::fail(VSP_ELAUNCH, "lpips_layer: memset failed");
-  if (C == 64 || C == 128 || C == 256) {   // register form: every element read once
-    const int lpp = C / 64, pxb = 4 * (64 / lpp);
-    int bx = (HW + pxb - 1) / pxb;
-    if (bx > 2048) bx = 2048;
-    if (lpp == 1) lpips_layer_reg_kernel<1, false><<<dim3(bx, B), 256, 0, st>>>(out, f0, f1, w, nullptr, HW, 1e-10f);
-    else if (lpp == 2) lpips_layer_reg_kernel<2, false><<<dim3(bx, B), 256, 0, st>>>(out, f0, f1, w, nullptr, HW, 1e-10f);
-    else lpips_layer_reg_kernel<4, false><<<dim3(bx, B), 256, 0, st>>>(out, f0, f1, w, nullptr, HW, 1e-10f);
-    return vsp::check_launch("lpips_layer");
-  }
-  int bx = (HW + 255) / 256;
-  if (bx > 1024) bx = 1024;
-  lpips_layer_fwd_kernel<<<dim3(bx, B), 256, 0, st>>>(out, f0, f1, w, C, HW, 1e-10f);
-  return vsp::check_launch("lpips_layer");
+  const bool reg = C == 64 || C == 128 || C == 256;   // register form: every element read once
+  const int lpp = C / 64, pxb = reg ? 4 * (64 / lpp) : 256;
+  int bx = (HW + pxb - 1) / pxb;
+  if (bx > (reg ? VSP_LPIPS_WORK_BLOCKS : 1024)) bx = reg ? VSP_LPIPS_WORK_BLOCKS : 1024;
+  if (work) VSP_REQUIRE(work_floats >= (int64_t)B * bx, "%s: work holds %lld floats, %lld needed (B * VSP_LPIPS_WORK_BLOCKS always suffices)", what,
+                        (long long)work_floats, (long long)B * bx);
+  else if (hipMemsetAsync(out, 0, sizeof(float) * B, st) != hipSuccess) return vsp::fail(VSP_ELAUNCH, "%s: memset failed", what);
+  if (!reg) lpips_layer_fwd_kernel<<<dim3(bx, B), 256, 0, st>>>(out, work, f0, f1, w, C, HW, 1e-10f);
+  else if (lpp == 1) lpips_layer_reg_kernel<1, false><<<dim3(bx, B), 256, 0, st>>>(out, work, f0, f1, w, nullptr, HW, 1e-10f);
+  else if (lpp == 2) lpips_layer_reg_kernel<2, false><<<dim3(bx, B), 256, 0, st>>>(out, work, f0, f1, w, nullptr, HW, 1e-10f);
+  else lpips_layer_reg_kernel<4, false><<<dim3(bx, B), 256, 0, st>>>(out, work, f0, f1, w, nullptr, HW, 1e-10f);
+  if (work) lpips_finish_kernel<<<B, 256, 0, st>>>(out, work, bx, HW);
+  return vsp::check_launch(what);
+}
+
+int vsp_lpips_layer_f32(float* out, const float* f0, const float* f1, const float* w, int B, int C, int HW, vsp_stream_t stream) {
+  return lpips_forward("lpips_layer", out, nullptr, 0, f0, f1, w, B, C, HW, stream);
+}
+
+int vsp_lpips_layer_ws_f32(float* out, float* work, int64_t work_floats, const float* f0, const float* f1, const float* w, int B, int C, int HW,
+                           vsp_stream_t stream) {
+  VSP_REQUIRE(work != nullptr || B == 0, "lpips_layer_ws: null work buffer");
+  return lpips_forward("lpips_layer_ws", out, work, work_floats, f0, f1, w, B, C, HW, stream);
 }
 
 int vsp_lpips_layer_bwd_f32(float* df1, const float* f0, const float* f1, const float* w, const float* gout, int B, int C, int HW,
@@ -368,9 +405,9 @@ int vsp_lpips_layer_bwd_f32(float* df1, const float* f0, const float* f1, const 
     int bx = (HW + pxb - 1) / pxb;
     if (bx > 4096) bx = 4096;
     hipStream_t st = vsp::as_stream(stream);
-    if (lpp == 1) lpips_layer_reg_kernel<1, true><<<dim3(bx, B), 256, 0, st>>>(df1, f0, f1, w, gout, HW, 1e-10f);
-    else if (lpp == 2) lpips_layer_reg_kernel<2, true><<<dim3(bx, B), 256, 0, st>>>(df1, f0, f1, w, gout, HW, 1e-10f);
-    else lpips_layer_reg_kernel<4, true><<<dim3(bx, B), 256, 0, st>>>(df1, f0, f1, w, gout, HW, 1e-10f);
+    if (lpp == 1) lpips_layer_reg_kernel<1, true><<<dim3(bx, B), 256, 0, st>>>(df1, nullptr, f0, f1, w, gout, HW, 1e-10f);
+    else if (lpp == 2) lpips_layer_reg_kernel<2, true><<<dim3(bx, B), 256, 0, st>>>(df1, nullptr, f0, f1, w, gout, HW, 1e-10f);
+    else lpips_layer_reg_kernel<4, true><<<dim3(bx, B), 256, 0, st>>>(df1, nullptr, f0, f1, w, gout, HW, 1e-10f);
     return vsp::check_launch("lpips_layer_bwd");
   }
   int bx = (HW + 255) / 256;

@@ -1183,6 +1183,9 @@ def maxpool2d_bwd(dy, x, k, s, p=0):
     return dx
 
 
+LPIPS_WORK_BLOCKS = 2048                     # include/vspbfr_hip.h VSP_LPIPS_WORK_BLOCKS
+
+
 def lpips_layer(f0, f1, w):
     """One LPIPS level: (B,) = spatial mean of sum_c w_c (unit(f0) - unit(f1))^2 over NCHW fp32 features."""
     f0, f1, w = _req(f0, "f0"), _req(f1, "f1"), _req(w, "w")
@@ -1190,7 +1193,8 @@ def lpips_layer(f0, f1, w):
     if f1.shape != f0.shape or w.numel() != Cc:
         raise RuntimeError("lpips_layer: f0 / f1 / w shapes do not match")
     out = torch.empty((B,), device=f0.device, dtype=torch.float32)
-    check(lib.vsp_lpips_layer_f32(_ptr(out), _ptr(f0), _ptr(f1), _ptr(w), B, Cc, H * W, _stream()), "lpips_layer")
+    work = torch.empty((B * LPIPS_WORK_BLOCKS,), device=f0.device, dtype=torch.float32)   # block sums, added in a fixed order (no atomics)
+    check(lib.vsp_lpips_layer_ws_f32(_ptr(out), _ptr(work), work.numel(), _ptr(f0), _ptr(f1), _ptr(w), B, Cc, H * W, _stream()), "lpips_layer")
     return out
 
 
