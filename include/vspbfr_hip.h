@@ -1323,6 +1323,39 @@ int vsp_parse_mask_u8(uint8_t* cls, uint8_t* keep, float* logits, int32_t* info,
 int vsp_parse_blur_u16(uint16_t* out, const uint8_t* keep, uint16_t* work, size_t work_bytes, int F, int S, const int32_t* taps, int R,
                        int border, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * FID on the device (csrc/fid.hip): pytorch-fid's Inception-v3 in fp32 on v_mfma_f32_16x16x4_f32.  Activations are
+ * (B, H, W, pitch) float, the images of a call back to back; a tensor is given as a pointer and a channel pitch, an output also as a
+ * channel offset, so that the branches of an Inception block write their slices of the concatenated tensor.
+ *   stem   y[slot] = ReLU(conv3x3 / 2 (resize(image) / 127.5 - 1) + b): 3 -> 32 without padding, fp32 fmaf.  The n images lie in `src` as
+ *          (h, w, 3) u8 at items[i].off; each is resized to (TH, TW) as F.interpolate(mode = "bilinear", align_corners = False) does,
+ *          without anti-aliasing (TH = h, TW = w reads the pixels themselves).  y is (B, (TH - 3) / 2 + 1, (TW - 3) / 2 + 1, 32).
+ *          w (27, 32), row (3 ky + kx) 3 + c; b (32).  items: host table, items_dev the same bytes on the device.
+ *   conv   out[.., c_off : c_off + Cout] = ReLU(conv(x) + bias): filter KH x KW one of 1x1, 3x3, 5x5, 1x7, 7x1, 1x3, 3x1, zero padding
+ *          (ph, pw) below the filter extent, stride 1 or 2, Cin and Cout multiples of 16.  x is (B, H, W, x_pitch) of which the first
+ *          Cin channels are read; out is (B, OH, OW, c_pitch), OH = (H + 2 ph - KH) / stride + 1.  w (KH, KW, Cin, Cout) fp32 with the
+ *          BatchNorm folded in, bias (Cout).  An output element is summed over (ky, kx, ci) in that order, in fmaf chains of 128
+ *          products that are then added in order: it has the same bits at any batch size and position.
+ *   pool   VSP_FID_POOL_MAX_S2: max 3x3 / 2 without padding; VSP_FID_POOL_AVG_S1: mean over the in-bounds taps of 3x3 / 1 / pad 1
+ *          (count_include_pad = False); VSP_FID_POOL_MAX_S1: max 3x3 / 1 / pad 1; VSP_FID_POOL_GLOBAL_AVG: (B, H, W, C) -> (B, C), the
+ *          pixels added in row-major order.  No atomics.
+ * VSP_EINVAL, nothing launched: a null pointer, channel counts that are not multiples of 16, a filter outside the list, a stride
+ * other than 1 or 2, padding >= the filter extent, an empty output, c_pitch < c_off + Cout, x_pitch < Cin, a pitch or offset that is
+ * no multiple of 4, a buffer off 16-byte alignment, an output that overlaps its input, an image outside `src`, a slot outside the
+ * batch.  VSP_ENOTSUP: a tensor of 2 GiB or more.  B = 0 (n = 0) returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_FID_POOL_MAX_S2 0
+#define VSP_FID_POOL_AVG_S1 1
+#define VSP_FID_POOL_MAX_S1 2
+#define VSP_FID_POOL_GLOBAL_AVG 3
+
+int vsp_fid_stem_u8(float* y, const uint8_t* src, size_t src_bytes, const vsp_det_src* items, const vsp_det_src* items_dev, int n, int B,
+                    int TH, int TW, const float* w, const float* b, vsp_stream_t stream);
+int vsp_fid_conv_f32(float* out, const float* x, const float* w, const float* bias, int B, int H, int W, int Cin, int x_pitch, int Cout,
+                     int KH, int KW, int ph, int pw, int stride, int c_off, int c_pitch, vsp_stream_t stream);
+int vsp_fid_pool_f32(float* out, const float* x, int B, int H, int W, int C, int x_pitch, int mode, int c_off, int c_pitch,
+                     vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,9 @@ SIGNATURES = {
     "vsp_parse_conv_f16": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p],
     "vsp_parse_mask_u8": [_p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p],
     "vsp_parse_blur_u16": [_p, _p, _p, C.c_size_t, _i, _i, _p, _i, _i, _p],
+    "vsp_fid_stem_u8": [_p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p, _p, _p],
+    "vsp_fid_conv_f32": [_p, _p, _p, _p] + [_i] * 13 + [_p],
+    "vsp_fid_pool_f32": [_p, _p] + [_i] * 8 + [_p],
 }
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],

@@ -2364,10 +2364,82 @@ def parse_blur_u16(keep, taps, border, out=None, work=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------------------ FID
+FID_POOL_MAX_S2, FID_POOL_AVG_S1, FID_POOL_MAX_S1, FID_POOL_GLOBAL_AVG = 0, 1, 2, 3      # include/vspbfr_hip.h VSP_FID_POOL_*
+FID_FILTERS = ((1, 1), (3, 3), (5, 5), (1, 7), (7, 1), (1, 3), (3, 1))
+
+
+def fid_conv_out(H, W, kh, kw, ph, pw, stride):
+    """the output map of fid_conv_f32"""
+    return (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
+
+
+def fid_pool_out(H, W, mode):
+    """the output map of fid_pool_f32"""
+    return ((H - 3) // 2 + 1, (W - 3) // 2 + 1) if mode == FID_POOL_MAX_S2 else (1, 1) if mode == FID_POOL_GLOBAL_AVG else (H, W)
+
+
+def _fid_view(t, name, B, H, W, C):
+    """(tensor, channel offset, pitch) -> the pointer of channel `offset` and the pitch, after checking that the tensor holds the
+    (B, H, W, pitch) image"""
+    buf, off, pitch = t
+    _req(buf, name)
+    off, pitch = int(off), int(pitch)
+    if off < 0 or off % 4 or pitch % 4 or off + C > pitch or buf.numel() < B * H * W * pitch:
+        raise RuntimeError(f"{name}: channels {off}..{off + C} of a pitch of {pitch}, {B} x {H} x {W} pixels in a tensor of {buf.numel()} floats")
+    return buf.data_ptr() + 4 * off, off, pitch
+
+
+def fid_stem_u8(y, src, items, items_dev, n, B, TH, TW, w, b):
+    """The first layer of the FID Inception on n u8 RGB images inside `src` (vsp_fid_stem_u8): bilinear resize to (TH, TW) without
+    anti-aliasing, x / 127.5 - 1, Conv2d_1a 3 -> 32 (3x3, stride 2) + b, ReLU.  y: a float32 tensor of B OH OW 32 elements, written at
+    the slots of `items` (a _lib.DetSrc array; items_dev the same bytes on the device).  w (27, 32), b (32).  Returns y."""
+    _req(y, "y"), _u8(src, "src"), _u8(items_dev, "items_dev"), _req(w, "w"), _req(b, "b")
+    oh, ow = (int(TH) - 3) // 2 + 1, (int(TW) - 3) // 2 + 1
+    if y.numel() != B * oh * ow * 32 or w.numel() != 27 * 32 or b.numel() != 32:
+        raise RuntimeError(f"fid_stem_u8: y of {y.numel()} floats for {B} x {oh} x {ow} x 32, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    if items_dev.numel() < n * C.sizeof(_lib.DetSrc):
+        raise RuntimeError("fid_stem_u8: items_dev is shorter than the item table")
+    check(lib.vsp_fid_stem_u8(_ptr(y), _ptr(src), src.numel(), C.cast(items, C.c_void_p), _ptr(items_dev), int(n), int(B), int(TH), int(TW),
+                              _ptr(w), _ptr(b), _stream()), "fid_stem_u8")
+    return y
+
+
+def fid_conv_f32(out, x, w, bias, B, H, W, stride=1, pad=(0, 0)):
+    """One convolution of the FID Inception (vsp_fid_conv_f32): ReLU(conv(x) + bias) on the fp32-input MFMA.  x and out are (tensor,
+    channel offset, pitch) triples over float32 tensors holding (B, H, W, pitch) and (B, OH, OW, pitch): the convolution reads Cin
+    channels from x's offset on and writes Cout channels from out's offset on.  w (KH, KW, Cin, Cout) float32, bias (Cout).  Returns
+    (OH, OW)."""
+    _req(w, "w"), _req(bias, "bias")
+    if w.dim() != 4 or bias.numel() != w.shape[3]:
+        raise RuntimeError(f"fid_conv_f32: w {tuple(w.shape)}, expected (KH, KW, Cin, Cout), and {bias.numel()} biases")
+    kh, kw, cin, cout = (int(v) for v in w.shape)
+    B, H, W, ph, pw = int(B), int(H), int(W), int(pad[0]), int(pad[1])
+    oh, ow = fid_conv_out(H, W, kh, kw, ph, pw, int(stride))
+    xp, _, x_pitch = _fid_view(x, "fid_conv_f32: x", B, H, W, cin)
+    _, c_off, c_pitch = _fid_view(out, "fid_conv_f32: out", B, max(oh, 0), max(ow, 0), cout)
+    check(lib.vsp_fid_conv_f32(_ptr(out[0]), C.c_void_p(xp), _ptr(w), _ptr(bias), B, H, W, cin, x_pitch, cout, kh, kw, ph, pw, int(stride), c_off,
+                               c_pitch, _stream()), "fid_conv_f32")
+    return oh, ow
+
+
+def fid_pool_f32(out, x, B, H, W, C_, mode):
+    """A pool of the FID Inception (vsp_fid_pool_f32) over C_ channels: FID_POOL_MAX_S2 (3x3 / 2), FID_POOL_AVG_S1 (3x3 / 1 / pad 1, the
+    mean of the in-bounds taps), FID_POOL_MAX_S1 (3x3 / 1 / pad 1) or FID_POOL_GLOBAL_AVG ((B, H, W, C) -> (B, C)).  x and out as in
+    fid_conv_f32.  Returns (OH, OW)."""
+    B, H, W, C_, mode = int(B), int(H), int(W), int(C_), int(mode)
+    oh, ow = fid_pool_out(H, W, mode)
+    xp, _, x_pitch = _fid_view(x, "fid_pool_f32: x", B, H, W, C_)
+    _, c_off, c_pitch = _fid_view(out, "fid_pool_f32: out", B, max(oh, 0), max(ow, 0), C_)
+    check(lib.vsp_fid_pool_f32(_ptr(out[0]), C.c_void_p(xp), B, H, W, C_, x_pitch, mode, c_off, c_pitch, _stream()), "fid_pool_f32")
+    return oh, ow
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types
-    skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check", "parse_conv_out"}
+    skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check", "parse_conv_out",
+            "fid_conv_out", "fid_pool_out"}
     g = globals()
     for name, obj in list(g.items()):
         if isinstance(obj, types.FunctionType) and not name.startswith("_") and name not in skip and obj.__module__ == __name__:

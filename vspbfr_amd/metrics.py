@@ -12,6 +12,7 @@ Windows: "gauss11" (11 x 11 Gaussian, sigma 1.5, population covariance: Wang et 
 and "uniform7" (7 x 7 box, sample covariance: scikit-image's defaults, what the reference's `dssim` computes)."""
 import json
 import math
+import os
 
 import torch
 
@@ -94,12 +95,23 @@ class Evaluator:
     `niqe` = (mu, cov) of a pristine model (`niqe.load_params`) adds the column `niqe`: the no-reference score of the restored image
     alone (one more launch per batch; the 36 x 36 finish runs on the host inside `report()`; an image without two usable blocks gets
     None).  With `niqe` and neither `lpips` nor `idloss`, `add(restored, None, names)` scores a batch that has no ground truth: its
-    rows hold `niqe` only."""
+    rows hold `niqe` only.
 
-    def __init__(self, window="gauss11", lpips=None, idloss=None, niqe=None, niqe_crop_border=0):
+    `fid` = (FidInception, (mu, sigma) or None[, the statistics' file name]) adds the top-level `fid` entry of the report (vspbfr_amd/fid.py):
+    `add` appends the batch's device features of the restored images -- and of the ground truth when the statistics are None --
+    without a host synchronisation; `report()` makes one more copy, computes the Frechet distance on the host and keeps the features
+    in `fid_features` (and `fid_gt_features`), in row order.  The rows do not change: FID is a property of the set.  With statistics,
+    `add(restored, None, names)` is legal like it is for NIQE."""
+
+    def __init__(self, window="gauss11", lpips=None, idloss=None, niqe=None, niqe_crop_border=0, fid=None):
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {WINDOWS} (got {window!r})")
         self.window, self.lpips, self.idloss, self.niqe, self.niqe_crop_border = window, lpips, idloss, niqe, niqe_crop_border
+        if fid is not None and (not isinstance(fid, (tuple, list)) or len(fid) not in (2, 3)):
+            raise ValueError("fid takes (FidInception, (mu, sigma) or None[, file name])")
+        self.fid = None if fid is None else (fid[0], fid[1], fid[2] if len(fid) == 3 else None)
+        self.fid_dev, self.fid_gt_dev = [], []   # per batch (B, 2048) float32 on the device
+        self.fid_features = self.fid_gt_features = None
         self.meta = []       # (index, lq, hq, samples per image; None without ground truth)
         self.dev = {"sse": [], "ssim": [], "lpips": [], "id": []}
         self.niqe_feats = []  # per batch (B, nblk, 36) float64 on the device
@@ -110,7 +122,9 @@ class Evaluator:
     def add(self, restored, gt, names=None, indices=None):
         from . import hip_ops as H
         if gt is None:
-            if self.niqe is None or self.lpips is not None or self.idloss is not None:
+            if self.fid is not None and self.fid[1] is None:
+                raise RuntimeError("Evaluator.add without ground truth: FID without reference statistics is measured against the ground truth")
+            if (self.niqe is None and self.fid is None) or self.lpips is not None or self.idloss is not None:
                 raise RuntimeError("Evaluator.add without ground truth needs an Evaluator that scores NIQE only (niqe=params, no lpips / idloss)")
             if self.dev["sse"]:
                 raise RuntimeError("Evaluator.add: this evaluator already holds batches with ground truth")
@@ -129,6 +143,10 @@ class Evaluator:
             raise RuntimeError(f"Evaluator.add: {B} images need {B} (lq, hq) name pairs and indices")
         if self.niqe is not None:
             self.niqe_feats.append(H.niqe_features_u8(restored, self.niqe_crop_border)[0])
+        if self.fid is not None:
+            self.fid_dev.append(self.fid[0].features(restored))
+            if self.fid[1] is None:
+                self.fid_gt_dev.append(self.fid[0].features(gt))
         if gt is None:
             self.meta.extend((i, n[0], n[1], None) for i, n in zip(indices, names))
             return
@@ -174,7 +192,73 @@ class Evaluator:
             if scores is not None:
                 row["niqe"] = scores[k]
             rows.append(row)
-        return summarize(rows, dataset, self.window)
+        report = summarize(rows, dataset, self.window)
+        if self.fid is not None:
+            n = len(self.meta)
+            # one more copy: the restored features and, against ground truth, the ground truth's behind them
+            both = torch.cat(self.fid_dev + self.fid_gt_dev).cpu().numpy() if n else None
+            order = sorted(range(n), key=lambda k: self.meta[k][0])          # the rows' order
+            self.fid_features = both[:n][order] if n else None
+            self.fid_gt_features = both[n:][order] if n and self.fid[1] is None else None
+            report["fid"] = fid_entry(self.fid_features, self.fid_gt_features, self.fid[1], self.fid[2])
+        return report
+
+
+def fid_entry(features, gt_features, ref_stats, ref_name):
+    """the report's `fid` entry from (n, 2048) features: against the ground truth's features, else against (mu, sigma); the value is
+    None below two images (a covariance needs two)"""
+    from .fid import frechet_distance, stats
+    n = 0 if features is None else int(features.shape[0])
+    against = "stats" if gt_features is None else "gt"
+    value = None
+    if n >= 2:
+        mu, sigma = stats(features)
+        rmu, rsigma = stats(gt_features) if gt_features is not None else ref_stats
+        value = frechet_distance(mu, sigma, rmu, rsigma)
+    return {"value": value, "count": n, "against": against, "ref": ref_name if against == "stats" else None}
+
+
+def fid_feature_dtype(dims=2048):
+    return [("index", "<i8"), ("features", "<f4", (dims,))]
+
+
+def fid_feature_path(report_path, gt=False):
+    """the feature file beside a report: metrics_<rank>.json -> fid_features_<rank>.npy (fid_features_<rank>_gt.npy for the ground truth)"""
+    d, base = os.path.split(report_path)
+    stem = os.path.splitext(base)[0]
+    stem = "fid_features_" + stem[len("metrics_"):] if stem.startswith("metrics_") else stem + "_fid_features"
+    return os.path.join(d, stem + ("_gt" if gt else "") + ".npy")
+
+
+def write_fid_features(path, indices, features):
+    """one record per image: its row's `index` and its float32 features (2048 of them from the FID Inception)"""
+    import numpy as np
+    features = np.zeros((0, 2048), dtype=np.float32) if features is None else np.asarray(features, dtype=np.float32)
+    if features.ndim != 2 or features.shape[0] != len(indices):
+        raise ValueError(f"write_fid_features: {len(indices)} indices for features {features.shape}")
+    rec = np.zeros(len(indices), dtype=fid_feature_dtype(features.shape[1]))
+    rec["index"] = np.asarray(indices, dtype=np.int64)
+    rec["features"] = features
+    with open(path, "wb") as f:
+        np.save(f, rec)
+
+
+def read_fid_features(path):
+    import numpy as np
+    rec = np.load(path, allow_pickle=False)
+    if rec.ndim != 1 or rec.dtype.names != ("index", "features") or rec.dtype != np.dtype(fid_feature_dtype(rec.dtype["features"].shape[0])):
+        raise ValueError(f"{path}: not a feature file (records of an int64 index and float32 features)")
+    return rec["index"], rec["features"]
+
+
+def write_report_with_features(ev, report, path):
+    """write_report, and the evaluator's FID features beside it when the report has a `fid` entry"""
+    write_report(report, path)
+    if "fid" in report:
+        idx = [r["index"] for r in report["images"]]
+        write_fid_features(fid_feature_path(path), idx, ev.fid_features)
+        if report["fid"]["against"] == "gt":
+            write_fid_features(fid_feature_path(path, gt=True), idx, ev.fid_gt_features)
 
 
 def write_report(report, path):
@@ -184,7 +268,9 @@ def write_report(report, path):
 
 
 def merge_reports(paths):
-    """Join the per-rank files of one dataset (pure host code): rows by index, means recomputed over all of them."""
+    """Join the per-rank files of one dataset (pure host code): rows by index, means recomputed over all of them.  When every file has
+    a `fid` entry and its feature file beside it, `fid` is recomputed from the concatenated features in index order; a mixture of files
+    with and without `fid`, or a missing feature file, is refused.  Files without `fid` merge as they always did."""
     reports = []
     for p in paths:
         with open(p) as f:
@@ -197,12 +283,44 @@ def merge_reports(paths):
     rows = [row for r in reports for row in r["images"]]
     if len({row["index"] for row in rows}) != len(rows):
         raise ValueError("merge_reports: an image index appears more than once")
-    return summarize(rows, reports[0]["dataset"], reports[0]["window"])
+    merged = summarize(rows, reports[0]["dataset"], reports[0]["window"])
+    with_fid = [r for r in reports if "fid" in r]
+    if with_fid:
+        import numpy as np
+        if len(with_fid) != len(reports):
+            raise ValueError("merge_reports: some files have a fid entry and some have none")
+        heads = {(r["fid"]["against"], r["fid"]["ref"]) for r in reports}
+        if len(heads) != 1:
+            raise ValueError(f"merge_reports: the files disagree on what fid is measured against: {sorted(map(str, heads))}")
+        against, ref = next(iter(heads))
+
+        def gather(gt):
+            idx, feats = [], []
+            for p, r in zip(paths, reports):
+                fp = fid_feature_path(p, gt)
+                if not os.path.exists(fp):
+                    raise ValueError(f"merge_reports: {p} has a fid entry but {fp} is missing")
+                i, f = read_fid_features(fp)
+                if sorted(i.tolist()) != sorted(row["index"] for row in r["images"]):
+                    raise ValueError(f"merge_reports: {fp} does not hold the images of {p}")
+                idx.append(i), feats.append(f)
+            idx, feats = np.concatenate(idx), np.concatenate(feats)
+            return feats[np.argsort(idx, kind="stable")]
+
+        ref_stats = None
+        if against == "stats":
+            from .fid import load_stats
+            ref_stats = load_stats(ref, dims=None)
+        merged["fid"] = fid_entry(gather(False), gather(True) if against == "gt" else None, ref_stats, ref)
+    return merged
 
 
 def summary_line(report):
     m = report["mean"]
     parts = [f"{c} {m[c]:.6g}" if m.get(c) is not None else f"{c} n/a" for c in COLUMNS if c in m]
+    if "fid" in report:
+        v = report["fid"]["value"]
+        parts.append("fid n/a" if v is None else f"fid {v:.6g}")
     return "metrics %s (%s, %d images, %d identical): %s" % (report["dataset"], report["window"], report["count"],
                                                             report["psnr_infinite"], ", ".join(parts))
 

@@ -2,7 +2,7 @@
 
     python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
         [--ingest host|device [--decode host|device]] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
-        [--niqe_params NPZ]
+        [--niqe_params NPZ] [--fid_weights W [--fid_stats S]]
 
 `vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
 puts it under this repository's rule that a feature leaves every existing `*_test.py` / `test_*.py` file as it is.  This module
@@ -14,7 +14,9 @@ summary line printed.  `--metrics` is off by default: without it the output dire
 `vspbfr_amd.restoration_test` (tests/test_metrics_cli_gpu.py compares the two).  `--metrics` with a dataset whose
 `--hq_data_list` entry is `None` is refused before anything is loaded -- unless `--niqe_params NPZ` (a pristine model:
 `vspbfr_amd.niqe_fit`) is given: then every report gains the no-reference `niqe` column of the restored image, and a dataset without
-ground truth gets a report with that column alone.  Multi-GPU as restoration_test; `metrics.merge_reports`
+ground truth gets a report with that column alone.  `--fid_weights W` adds the report's `fid` entry (against the ground truth,
+or against `--fid_stats S`, which also lets a dataset without ground truth be scored) and writes `fid_features_<rank>.npy` beside the
+report.  Multi-GPU as restoration_test; `metrics.merge_reports`
 joins the per-rank files."""
 import argparse
 import os
@@ -63,7 +65,10 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
         from .metrics import Evaluator
         niqe_params = getattr(args, "niqe_model", None)
         # a dataset without ground truth is scored by NIQE alone (main() has refused it already when no model was given)
-        evaluator = Evaluator(args.ssim_window, *args.scorers, niqe=niqe_params) if data.hq is not None else Evaluator(args.ssim_window, niqe=niqe_params)
+        fid = getattr(args, "fid", None)
+        kw = {} if fid is None else {"fid": fid}
+        evaluator = Evaluator(args.ssim_window, *args.scorers, niqe=niqe_params, **kw) if data.hq is not None else Evaluator(
+            args.ssim_window, niqe=niqe_params, **kw)
     print("testing!!! len:%d (rank %d handles %d..%d)" % (len(data), rank, lo, hi))
     with torch.no_grad():
         for idx, low, gts in _batches(args, data, lo, hi, device):
@@ -79,9 +84,9 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
                     evaluator.add(u8["restore"], None, [(os.path.relpath(data.lq[i], lq_root), None) for i in idx], idx)
     writer.drain()
     if evaluator is not None:
-        from .metrics import summary_line, write_report
+        from .metrics import summary_line, write_report_with_features
         report = evaluator.report(data_name)
-        write_report(report, os.path.join(eval_dict, "metrics_%d.json" % rank))
+        write_report_with_features(evaluator, report, os.path.join(eval_dict, "metrics_%d.json" % rank))      # + fid_features_<rank>.npy with FID
         print(summary_line(report))
     return eval_dict
 
@@ -124,7 +129,24 @@ def main(argv=None):
     ap.add_argument("--niqe_params", type=str, default=None,
                     help="extension: .npz pristine model (mu_pris_param, cov_pris_param; python -m vspbfr_amd.niqe_fit); adds the no-reference "
                          "niqe column and lets a dataset without ground truth be scored by it alone")
+    ap.add_argument("--fid_weights", type=str, default=None,
+                    help="extension: FID Inception state dict (pt_inception layout); adds the report's fid entry and writes "
+                         "fid_features_<rank>.npy beside metrics_<rank>.json")
+    ap.add_argument("--fid_stats", type=str, default=None,
+                    help="extension: .npz or torch file with mu / sigma: FID against these statistics instead of the ground truth; lets a "
+                         "dataset without ground truth be scored")
     args = ap.parse_args(argv)
+    if not args.metrics and (args.fid_weights or args.fid_stats):
+        ap.error("--fid_weights / --fid_stats only have a meaning with --metrics")
+    if args.fid_stats and not args.fid_weights:
+        ap.error("--fid_stats only has a meaning with --fid_weights")
+    args.fid_ref = None
+    if args.fid_stats:
+        from .fid import load_stats
+        try:
+            args.fid_ref = load_stats(args.fid_stats)
+        except (ValueError, OSError) as e:
+            ap.error(str(e))
     if args.decode is not None and args.ingest != "device":
         ap.error("--decode only has a meaning with --ingest device")
     if not args.metrics and (args.lpips_weights or args.id_weights):
@@ -140,7 +162,9 @@ def main(argv=None):
             ap.error(str(e))
     if args.metrics:
         missing = [d["name"] for d in get_store_data(args.lq_data_list, args.hq_data_list, args.data_name_list) if d["hq"] in ("None", "")]
-        if missing and args.niqe_model is None:
+        if missing and args.fid_weights and args.fid_ref is None:
+            ap.error("--fid_weights without --fid_stats measures against ground truth; none given for: " + ", ".join(missing))
+        if missing and args.niqe_model is None and args.fid_ref is None:
             ap.error("--metrics needs a ground-truth root (--hq_data_list) for every dataset; none given for: " + ", ".join(missing))
     args.latent, args.n_mlp = 512, 8
     from . import hip_ops
@@ -166,6 +190,9 @@ def main(argv=None):
     if args.metrics:
         from .metrics import load_scorers
         args.scorers = load_scorers(args.lpips_weights, args.id_weights, device)
+        if args.fid_weights:
+            from . import fid as fid_mod
+            args.fid = (fid_mod.FidInception(fid_mod.load(args.fid_weights), device), args.fid_ref, args.fid_stats)
     for k, d in enumerate(store):
         diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
         pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)

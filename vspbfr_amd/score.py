@@ -2,10 +2,15 @@
 `python -m vspbfr_amd.restoration_metrics`): what someone comparing against another method's outputs needs.
 
     python -m vspbfr_amd.score --restored eval_dir/.../demo --gt eval_dir/.../demo [--pattern _restore.png/_gt.png]
-        [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--niqe_params NPZ] [--batch 8] [--out metrics.json]
+        [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--niqe_params NPZ]
+        [--fid_weights W [--fid_stats S]] [--batch 8] [--out metrics.json]
 
 `--niqe_params` (a pristine model, `vspbfr_amd.niqe_fit` or a published one) adds the no-reference `niqe` column and makes --gt
 optional: without --gt every file of --restored that carries the restored suffix (all files when none does) is scored alone.
+
+`--fid_weights` (an FID Inception state dict, `vspbfr_amd.fid`) adds the report's top-level `fid` entry: against the ground truth's
+features, or against `--fid_stats` (mu / sigma of a reference set), which makes --gt optional too.  With --out the features go to
+`<out stem>_fid_features.npy` (and `..._gt.npy`) beside the report, so that `metrics.merge_reports` can recompute the distance.
 
 Pairing: a file `<stem><restored suffix>` of --restored goes with `<stem><gt suffix>` of --gt (the CLI's own naming,
 `{index}_{rank}_{name}_restore.png` / `..._gt.png`); when no file of --restored carries the suffix, the two folders are
@@ -55,13 +60,16 @@ def restored_files(restored_dir, pattern="_restore.png/_gt.png"):
     return [(p, None) for p in (tagged or files)]
 
 
-def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda", niqe=None):
+def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda", niqe=None, fid=None, evaluator=None):
     """The report of a list of (restored, gt) files; images of one size are batched, an odd one goes alone.  gt = None in every
-    pair (with `niqe` params): the no-reference report."""
+    pair (with `niqe` params or `fid` statistics): the no-reference report.  `fid`: metrics.Evaluator's argument; `evaluator`: a list
+    that receives the Evaluator (its FID features go to disk beside the report)."""
     import torch
 
     from .metrics import Evaluator
-    ev = Evaluator(window, lpips, idloss, niqe)
+    ev = Evaluator(window, lpips, idloss, niqe) if fid is None else Evaluator(window, lpips, idloss, niqe, fid=fid)
+    if evaluator is not None:
+        evaluator.append(ev)
     pend, shape = [], None
 
     def flush():
@@ -86,24 +94,33 @@ def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, datas
 def main(argv=None):
     ap = argparse.ArgumentParser(description="PSNR / SSIM / LPIPS / ID of a folder of restored PNGs against ground truth (MI355X)")
     ap.add_argument("--restored", required=True)
-    ap.add_argument("--gt", default=None, help="ground-truth folder; optional with --niqe_params")
+    ap.add_argument("--gt", default=None, help="ground-truth folder; optional with --niqe_params or --fid_stats")
     ap.add_argument("--pattern", default="_restore.png/_gt.png", help="RESTORED_SUFFIX/GT_SUFFIX")
     ap.add_argument("--ssim_window", choices=["gauss11", "uniform7"], default="gauss11")
     ap.add_argument("--lpips_weights", default=None, help="LIN[,VGG] weight files; adds the lpips column")
     ap.add_argument("--id_weights", default=None, help="resnet101(256) state dict; adds the id column")
     ap.add_argument("--niqe_params", default=None, help=".npz with mu_pris_param / cov_pris_param; adds the niqe column")
+    ap.add_argument("--fid_weights", default=None, help="FID Inception state dict (pt_inception layout); adds the report's fid entry")
+    ap.add_argument("--fid_stats", default=None, help=".npz or torch file with mu / sigma: FID against these statistics instead of --gt")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dataset", default=None, help="name written into the report")
     ap.add_argument("--out", default=None, help="write the JSON report here (default: print it)")
     args = ap.parse_args(argv)
     if args.batch < 1:
         ap.error("--batch must be at least 1")
-    if args.gt is None and not args.niqe_params:
+    if args.fid_stats and not args.fid_weights:
+        ap.error("--fid_stats only has a meaning with --fid_weights")
+    if args.gt is None and args.fid_weights and not args.fid_stats:
+        ap.error("--fid_weights without --fid_stats measures against ground truth: it needs --gt")
+    if args.gt is None and not args.niqe_params and not args.fid_stats:
         ap.error("--gt is required unless --niqe_params asks for the no-reference score")
     if args.gt is None and (args.lpips_weights or args.id_weights):
         ap.error("--lpips_weights / --id_weights compare against ground truth: they need --gt")
-    niqe_params = None
+    niqe_params = fid_stats = None
     try:
+        if args.fid_stats:
+            from .fid import load_stats
+            fid_stats = load_stats(args.fid_stats)
         if args.niqe_params:
             from .niqe import load_params
             niqe_params = load_params(args.niqe_params)
@@ -112,8 +129,15 @@ def main(argv=None):
         ap.error(str(e))
     from .metrics import load_scorers, summary_line, write_report
     lp, idl = load_scorers(args.lpips_weights, args.id_weights)
-    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset, niqe=niqe_params)
-    if args.out:
+    fid, held = None, []
+    if args.fid_weights:
+        from . import fid as fid_mod
+        fid = (fid_mod.FidInception(fid_mod.load(args.fid_weights), "cuda"), fid_stats, args.fid_stats)
+    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset, niqe=niqe_params, fid=fid, evaluator=held)
+    if args.out and fid is not None:
+        from .metrics import write_report_with_features
+        write_report_with_features(held[0], report, args.out)
+    elif args.out:
         write_report(report, args.out)
     else:
         print(json.dumps(report, indent=1, allow_nan=False))
