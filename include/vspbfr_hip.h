@@ -1356,6 +1356,45 @@ int vsp_fid_conv_f32(float* out, const float* x, const float* w, const float* bi
 int vsp_fid_pool_f32(float* out, const float* x, int B, int H, int W, int C, int x_pitch, int mode, int c_off, int c_pitch,
                      vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Background upscaling with Real-ESRGAN's RRDBNet (csrc/rrdb.hip): x4plus / x2plus, 64 features, growth 32, f16 operands and
+ * fp32 accumulation.  One call serves one unit (a photo or a row band).  Activations are (H, W, pitch) _Float16: a tensor is a pointer
+ * and a channel pitch, an output also a channel offset, so a dense block is one 192-channel tensor.  Every convolution is 3x3, stride 1,
+ * zero padding 1.
+ *   head   y = conv_first(net_in) + b, 3 | 12 -> 64 in fp32 fmaf.  The photo lies in `src` as (h, w, 3) u8 at byte src_off.  scale 4:
+ *          net_in = photo / 255, (h, w, 3).  scale 2: the photo padded by reflection to even sides (row h -> h - 2, column w -> w - 2)
+ *          and pixel-unshuffled by 2, channel 4 c + 2 dy + dx, (ceil(h / 2), ceil(w / 2), 12), all as index arithmetic.  Rows
+ *          row0 .. row0 + rows - 1 of the network's input map are written, row row0 at y, y_pitch halves per pixel (channels 0 .. 63).
+ *          wt (9 Cin, 64) fp32, row (3 ky + kx) Cin + channel; b (64).
+ *   conv   y[.., y_off : y_off + Cout] = f16(s2 (s1 v + r1) + r2), v = [LeakyReLU 0.2] (conv3x3(x[.., 0 : Cin]) + b), on
+ *          v_mfma_f32_16x16x32_f16; each residual step is optional (r1 / r2 null), fmaf(s, v, r) in fp32.  x is (H, W, x_pitch); with
+ *          VSP_RRDB_UP the convolution sees its nearest x2, (y >> 1, x >> 1), and the output map is (2 H, 2 W), else (H, W).
+ *          Cin in {64, 96, 128, 160, 192}, Cout in {32, 64}.  y may be x itself (same pointer, same pitch, no UP) when y_off >= Cin:
+ *          conv1 .. conv4 of a dense block write their slices behind the channels they read.  A residual is (ptr, pitch, scale) and
+ *          reads channels 0 .. Cout - 1; it may lie in the output tensor only at the same pointer and pitch with y_off >= Cout.
+ *          w_img: the f16 image of rrdb.pack_conv_weight, (Cin / 32, 9, Cout / 16, 64, 8): element j of lane l of block nb of tap t of
+ *          chunk kc = w[co = 16 nb + (l & 15)][ci = 32 kc + 8 (l >> 4) + j][ky = t / 3][kx = t % 3].  b: fp32 (Cout).
+ *   tail   v = conv_last(x) + b, 64 -> 3 (w_img (2, 9, 1, 64, 8), Cout zero-padded to 16; b padded to 16); byte = rintf(255 clamp(v, 0, 1)).
+ *          Rows keep0 .. keep0 + keepn - 1 and columns 0 .. out_w - 1 of the (H, W) map are written, row keep0 at out + out_off, rows
+ *          out_pitch bytes apart (the x2 crop is out_w < W and a keep window that ends early).  out_f32 (or null): one float per byte
+ *          of out, takes v unclamped.  A non-finite v is written as 0 and ORs VSP_RRDB_NONFINITE into info[0] (zeroed by the caller).
+ * VSP_EINVAL, nothing launched: a null pointer, channel counts outside the lists, a pitch below the channels used or no multiple of 4
+ * halves (8 for a tensor that is read as a convolution input), a misaligned buffer (16 bytes for convolution inputs, weights and
+ * biases, 8 for outputs and residuals), an output slice that overlaps the channels read, an aliased residual, a window outside the
+ * unit, bytes outside src / out, h or w < 1, an odd side of 1 at scale 2.  VSP_ENOTSUP: a tensor of 2 GiB or more.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_RRDB_NONFINITE 1           /* info bit: a value was not finite before the clamp */
+#define VSP_RRDB_ACT 1                 /* conv flags */
+#define VSP_RRDB_UP 2
+
+int vsp_rrdb_head_u8(void* y, int y_pitch, const uint8_t* src, size_t src_bytes, int64_t src_off, int h, int w, int scale, int row0, int rows,
+                     const float* wt, const float* b, vsp_stream_t stream);
+int vsp_rrdb_conv_f16(void* y, int y_pitch, int y_off, const void* x, int x_pitch, int H, int W, int Cin, int Cout, int flags,
+                      const void* w_img, const float* b, const void* r1, int r1_pitch, float s1, const void* r2, int r2_pitch, float s2,
+                      vsp_stream_t stream);
+int vsp_rrdb_tail_u8(uint8_t* out, size_t out_bytes, int64_t out_off, int64_t out_pitch, int out_w, float* out_f32, int32_t* info,
+                     const void* x, int x_pitch, int H, int W, int keep0, int keepn, const void* w_img, const float* b, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2435,6 +2435,78 @@ def fid_pool_f32(out, x, B, H, W, C_, mode):
     return oh, ow
 
 
+# ------------------------------------------------------------------------------------------------- RRDBNet upscaling
+RRDB_NONFINITE, RRDB_ACT, RRDB_UP = 1, 1, 2      # include/vspbfr_hip.h VSP_RRDB_*
+
+
+def _rrdb_act(t, name, need):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16 or t.dim() != 1 or not t.is_contiguous() or t.numel() < need:
+        raise RuntimeError(f"{name} must be a flat contiguous CUDA float16 tensor of at least {need} elements")
+    return t
+
+
+def rrdb_head_u8(y, y_pitch, src, src_off, h, w, scale, w_pack, b, row0=0, rows=None):
+    """RRDBNet's conv_first on the u8 photo (h, w, 3) at byte src_off of the flat uint8 `src` (vsp_rrdb_head_u8): rows row0 .. row0 + rows
+    - 1 of the network's input map -- (h, w) at scale 4, (ceil(h / 2), ceil(w / 2)) behind the pixel unshuffle at scale 2 -- go to y, a flat
+    float16 buffer with y_pitch halves per pixel, channels 0 .. 63.  w_pack (27 | 108, 64), b (64) float32.  Returns (rows, map width)."""
+    h, w, scale, y_pitch = int(h), int(w), int(scale), int(y_pitch)
+    nh, nw = (h, w) if scale == 4 else ((h + 1) // 2, (w + 1) // 2)
+    rows = nh - int(row0) if rows is None else int(rows)
+    _u8(src, "src"), _req(w_pack, "w_pack"), _req(b, "b")
+    if w_pack.numel() != (27 if scale == 4 else 108) * 64 or b.numel() != 64:
+        raise RuntimeError(f"rrdb_head_u8: scale {scale}: w_pack {tuple(w_pack.shape)}, b {tuple(b.shape)}")
+    _rrdb_act(y, "y", max(rows, 0) * nw * y_pitch)
+    check(lib.vsp_rrdb_head_u8(_ptr(y), y_pitch, _ptr(src), src.numel(), int(src_off), h, w, scale, int(row0), rows, _ptr(w_pack), _ptr(b),
+                               _stream()), "rrdb_head_u8")
+    return rows, nw
+
+
+def rrdb_conv_f16(y, y_pitch, y_off, x, x_pitch, H, W, w_img, b, act=False, up=False, res1=None, res2=None):
+    """One 3x3 convolution of RRDBNet (vsp_rrdb_conv_f16): x, a flat float16 buffer holding (H, W, x_pitch), is read in its channels
+    0 .. Cin - 1; channels y_off .. y_off + Cout - 1 of y, (OH, OW, y_pitch) with (OH, OW) = (2 H, 2 W) under `up` (nearest x2 of the
+    input) and (H, W) otherwise, take f16(s2 (s1 v + r1) + r2) with v = [LeakyReLU 0.2] (conv(x) + b).  res1, res2: None or (flat float16
+    tensor, pitch, scale).  y may be x when y_off >= Cin.  w_img: rrdb.pack_conv_weight's image (Cin / 32, 9, Cout / 16, 64, 8); b float32
+    (Cout).  Returns y."""
+    H, W, y_pitch, y_off, x_pitch = int(H), int(W), int(y_pitch), int(y_off), int(x_pitch)
+    if not isinstance(w_img, torch.Tensor) or not w_img.is_cuda or w_img.dtype != torch.float16 or not w_img.is_contiguous() or w_img.dim() != 5 \
+            or tuple(w_img.shape[3:]) != (64, 8) or w_img.shape[1] != 9:
+        raise RuntimeError("rrdb_conv_f16: w_img must be a contiguous CUDA float16 image (Cin / 32, 9, Cout / 16, 64, 8)")
+    cin, cout = 32 * int(w_img.shape[0]), 16 * int(w_img.shape[2])
+    _req(b, "b")
+    if b.numel() != cout:
+        raise RuntimeError(f"rrdb_conv_f16: {b.numel()} biases for {cout} channels")
+    oh, ow = (2 * H, 2 * W) if up else (H, W)
+    _rrdb_act(x, "x", H * W * x_pitch), _rrdb_act(y, "y", oh * ow * y_pitch)
+    r = []
+    for res, name in ((res1, "res1"), (res2, "res2")):
+        if res is None:
+            r += [None, 0, 0.0]
+        else:
+            r += [_ptr(_rrdb_act(res[0], name, oh * ow * int(res[1]))), int(res[1]), float(res[2])]
+    check(lib.vsp_rrdb_conv_f16(_ptr(y), y_pitch, y_off, _ptr(x), x_pitch, H, W, cin, cout, (RRDB_ACT if act else 0) | (RRDB_UP if up else 0),
+                                _ptr(w_img), _ptr(b), r[0], r[1], r[2], r[3], r[4], r[5], _stream()), "rrdb_conv_f16")
+    return y
+
+
+def rrdb_tail_u8(out, out_off, out_pitch, out_w, info, x, x_pitch, H, W, keep0, keepn, w_img, b, out_f32=None):
+    """RRDBNet's conv_last and the quantisation (vsp_rrdb_tail_u8): x holds (H, W, x_pitch) float16; rows keep0 .. keep0 + keepn - 1 and
+    columns 0 .. out_w - 1 of clamp(conv(x) + b) go as rintf(255 v) bytes to the flat uint8 `out`, row keep0 at byte out_off, rows
+    out_pitch bytes apart.  info: a CUDA int32 tensor of one word, zeroed by the caller, takes RRDB_NONFINITE.  w_img (2, 9, 1, 64, 8)
+    float16, b float32 (16, the last 13 zero).  out_f32: a flat float32 tensor of out's size or None.  Returns out."""
+    H, W, x_pitch = int(H), int(W), int(x_pitch)
+    _u8(out, "out"), _rrdb_act(x, "x", H * W * x_pitch), _req(b, "b"), _opt(out_f32, "out_f32")
+    if not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or not info.is_cuda or not info.is_contiguous() or info.numel() < 1:
+        raise RuntimeError("rrdb_tail_u8: info must be a contiguous CUDA int32 tensor")
+    if not isinstance(w_img, torch.Tensor) or not w_img.is_cuda or w_img.dtype != torch.float16 or not w_img.is_contiguous() \
+            or w_img.numel() != 2 * 9 * 64 * 8 or b.numel() != 16:
+        raise RuntimeError("rrdb_tail_u8: w_img must be a contiguous CUDA float16 image of 2 x 9 x 1 x 64 x 8, b of 16 values")
+    if out_f32 is not None and out_f32.numel() != out.numel():
+        raise RuntimeError("rrdb_tail_u8: out_f32 must have one float per byte of out")
+    check(lib.vsp_rrdb_tail_u8(_ptr(out), out.numel(), int(out_off), int(out_pitch), int(out_w), _ptr(out_f32), _ptr(info), _ptr(x), x_pitch,
+                               H, W, int(keep0), int(keepn), _ptr(w_img), _ptr(b), _stream()), "rrdb_tail_u8")
+    return out
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types

@@ -60,7 +60,9 @@ csrc/sr.hip) from the checkpoint W instead of the LANCZOS resize -- n
 expects is unverified against a real file.  A x4 network at --upscale 2 goes through the device LANCZOS resize down from its x4 output;
 a x2 network at --upscale 4 is refused.  --bg_band_rows N processes every photo in bands of N rows (the same bytes).  report.json then
 lists `background` = {model, num_conv, scale, banded, nonfinite}; `nonfinite` names the photos in which a value was not finite before the
-clamp (written as 0): a warning, not an abort.  Without the flag nothing changes.
+clamp (written as 0): a warning, not an abort.  Without the flag nothing changes.  A checkpoint with RRDBNet's keys (`conv_first.weight`:
+RealESRGAN_x4plus, RealESRGAN_x2plus, the 6-block anime model) runs that network instead (vspbfr_amd.rrdb, csrc/rrdb.hip) under
+the same rules; `background` is then {model: "RRDBNet", num_block, scale, banded, nonfinite}.
 
 --parse_weights W: the paste goes through a face-parsing mask (vspbfr_amd.parse, csrc/parse.hip): facexlib's ParseNet from the
 checkpoint W runs on the network's restored crop, the face classes are kept (everything but background, neck, clothes, hair and hat), the
@@ -306,7 +308,7 @@ def main(argv=None):
     ap.add_argument("--png_encode", choices=["host", "device"], default=None,
                     help="code the PNG files with Pillow on the host (the default) or on the device; equal pixels")
     ap.add_argument("--bg_weights", type=str, default=None,
-                    help="SRVGGNetCompact checkpoint (not shipped): upscale the photo under the faces with it instead of LANCZOS; needs --upscale 2 or 4")
+                    help="SRVGGNetCompact or RRDBNet (x4plus / x2plus) checkpoint (not shipped): upscale the photo under the faces with it instead of LANCZOS; needs --upscale 2 or 4")
     ap.add_argument("--bg_band_rows", type=int, default=None, help="--bg_weights: process every photo in bands of this many rows (the same bytes)")
     ap.add_argument("--parse_weights", type=str, default=None,
                     help="ParseNet checkpoint (not shipped): paste through the face-parsing mask of the restored crop instead of the whole square")
@@ -377,8 +379,8 @@ def main(argv=None):
     restorer = PhotoRestorer(pipe, args.batch, upscale=args.upscale, size=args.size, inset=args.inset, feather=args.feather,
                              antialias=args.antialias, color_fix=color_fix, color_levels=color_levels)
     if bg_state is not None:
-        from .upscale import SrUpscaler
-        restorer.background = SrUpscaler(bg_state, device, band_rows=args.bg_band_rows)
+        from .upscale import make_upscaler
+        restorer.background = make_upscaler(bg_state, device, band_rows=args.bg_band_rows)
     if parse_state is not None:
         from .parse import FaceParser
         restorer.parser, restorer.parse_taps, restorer.parse_border = FaceParser(parse_state, device), parse_taps, parse_border

@@ -12,6 +12,9 @@ x4 output, as Real-ESRGAN does for an `outscale` below the network's.
     plan_bands                                 row bands with a halo of the network's receptive radius: a banded run equals the unbanded bytes
     SrUpscaler                                 weights -> upscale() / upscale_to()
 
+A checkpoint with RRDBNet's keys (`conv_first.weight`: RealESRGAN_x4plus, RealESRGAN_x2plus) is handed to vspbfr_amd.rrdb by
+check_background_arguments and make_upscaler; check_state_dict and load here serve the compact network alone.
+
 **No weights are shipped.  The key layout is written from the public model definition and could not be checked against a real checkpoint
 file**; a file that deviates is refused by key name, never half-loaded.
 
@@ -321,9 +324,29 @@ class SrUpscaler:
         return {"model": MODEL_NAME, "num_conv": self.num_conv, "scale": self.scale, "banded": bool(banded), "nonfinite": list(nonfinite)}
 
 
+def is_rrdb_state(sd):
+    """whether a loaded checkpoint, behind its optional wrapper and `module.` prefix, has RRDBNet's `conv_first.weight`"""
+    if not isinstance(sd, dict):
+        return False
+    for wrapper in ("params_ema", "params"):
+        if wrapper in sd and isinstance(sd[wrapper], dict):
+            sd = sd[wrapper]
+            break
+    return any(str(k) in ("conv_first.weight", "module.conv_first.weight") for k in sd)
+
+
+def make_upscaler(state, device, band_rows=None):
+    """the upscaler of a checked state: rrdb.RrdbUpscaler for an RrdbState, SrUpscaler for an SrState"""
+    if isinstance(state, SrState):
+        return SrUpscaler(state, device, band_rows=band_rows)
+    from .rrdb import RrdbUpscaler
+    return RrdbUpscaler(state, device, band_rows=band_rows)
+
+
 def check_background_arguments(ap, weights, upscale, band_rows=None):
-    """The checks both CLIs make before any model goes to the device -> SrState; ap.error for a missing file, a checkpoint the loader
-    refuses, an output scale the network cannot fill (None: the network's own) and a band of less than one row."""
+    """The checks both CLIs make before any model goes to the device -> SrState, or rrdb.RrdbState for a checkpoint with RRDBNet's keys
+    (the file is opened once); ap.error for a missing file, a checkpoint the loader refuses, an output scale the network cannot fill
+    (None: the network's own) and a band of less than one row."""
     if upscale is not None and upscale not in (2, 4):
         ap.error(f"background upscaling needs an upscale of 2 or 4, not {upscale}")
     if band_rows is not None and band_rows < 1:
@@ -331,7 +354,12 @@ def check_background_arguments(ap, weights, upscale, band_rows=None):
     if not os.path.isfile(weights):
         ap.error(f"no such file: {weights}")
     try:
-        state = load(weights)
+        sd = torch.load(weights, map_location="cpu")
+        if is_rrdb_state(sd):
+            from . import rrdb
+            state = rrdb.check_state_dict(sd)
+        else:
+            state = check_state_dict(sd)
     except ValueError as e:
         ap.error(str(e))
     if upscale is not None and state.scale < upscale:
@@ -340,9 +368,10 @@ def check_background_arguments(ap, weights, upscale, band_rows=None):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description="Upscale photos with Real-ESRGAN's compact network on the device")
+    ap = argparse.ArgumentParser(description="Upscale photos with Real-ESRGAN's compact network or its RRDBNet on the device")
     ap.add_argument("--photos", type=str, required=True, help="directory of photos (searched recursively)")
-    ap.add_argument("--weights", type=str, required=True, help="SRVGGNetCompact checkpoint, 64 features (not shipped)")
+    ap.add_argument("--weights", type=str, required=True,
+                    help="SRVGGNetCompact checkpoint, 64 features, or RRDBNet checkpoint (x4plus, x2plus: 64 features, growth 32); not shipped")
     ap.add_argument("--out", type=str, required=True, help="output directory")
     ap.add_argument("--scale", type=int, choices=[2, 4], default=None, help="output scale (default: the network's)")
     ap.add_argument("--format", choices=["png", "jpg"], default="png", help="file format of the output photos")
@@ -358,7 +387,7 @@ def main(argv=None):
         ap.error(str(e))
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
-    net = SrUpscaler(state, device, band_rows=args.band_rows)
+    net = make_upscaler(state, device, band_rows=args.band_rows)
     if args.format == "jpg":
         from .jpeg import DEFAULT_QUALITY
         writer = JpegWriter(quality=DEFAULT_QUALITY, subsampling="420", encode="device")
