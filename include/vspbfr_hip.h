@@ -1395,6 +1395,41 @@ int vsp_rrdb_conv_f16(void* y, int y_pitch, int y_off, const void* x, int x_pitc
 int vsp_rrdb_tail_u8(uint8_t* out, size_t out_bytes, int64_t out_off, int64_t out_pitch, int out_w, float* out_f32, int32_t* info,
                      const void* x, int x_pitch, int H, int W, int keep0, int keepn, const void* w_img, const float* b, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Face detection with RetinaFace's ResNet-50 network (csrc/detect_r50.hip): f16 operands, fp32 accumulation and biases.
+ * Activations are (B, H, W, pitch) _Float16: a tensor is a pointer, a channel pitch and a channel offset.  The post-processing is
+ * vsp_det_decode_nms_f32.
+ *   stem   y[slot] = f16(relu(conv7x7/2/pad3(canvas) + b)), 3 -> 64 in fp32 fmaf, for the n photos of `items` (as vsp_det_entry_u8: u8
+ *          RGB inside `src`, swapped to BGR, minus (104, 117, 123), 0 outside the photo).  y is (B, ceil(Hc / 2), ceil(Wc / 2), 64).
+ *          w (147, 64) fp32, row (7 ky + kx) 3 + channel (B, G, R); b (64).
+ *   pool   3x3 / 2 / pad 1 maximum over the taps inside the map: (B, H, W, C) -> (B, ceil(H / 2), ceil(W / 2), C), both dense.
+ *   conv   y[.., y_off : y_off + Cout] = f16([relu](conv(x[.., x_off : x_off + Cin]) + b [+ res]) [+ up]) on v_mfma_f32_16x16x32_f16.
+ *          ksize 1 (no padding) or 3 (padding 1), stride 1 or 2, output map ((H - 1) / stride + 1, (W - 1) / stride + 1); Cin and Cout
+ *          multiples of 64 up to 2048.  res (ptr, pitch, offset) is read at the output pixel and may be the very window written (same
+ *          pointer, pitch and offset: the bottleneck's sum replaces its identity).  up (ptr, pitch, offset) is an (OH / 2, OW / 2) map
+ *          read at (oy >> 1, ox >> 1); OH and OW must be even.  The sum over taps and channels has one fixed order per output pixel:
+ *          an image's result depends neither on the batch size nor on its position in the batch.
+ *          w_img: the f16 image of detect_r50.pack_conv_weight, (ksize^2, Cin / 32, Cout / 16, 64, 8): element j of lane l of block nb of
+ *          step kc of tap t = w[co = 16 nb + (l & 15)][ci = 32 kc + 8 (l >> 4) + j][ky = t / ksize][kx = t % ksize].  b: fp32 (Cout).
+ *   heads  the class (4), box (8) and landmark (20) 1x1 heads of one level in fp32 fmaf on channels 0 .. 255 of x: cell (i, j) of image
+ *          b writes priors p0 + 2 (i W + j) + {0, 1} of conf (B, P, 2), loc (B, P, 4), lm (B, P, 10).  w (256, 32), b (32) fp32.
+ * VSP_EINVAL, nothing launched: a null pointer, a channel count, filter, stride or flag that is not served, a channel window outside
+ * its pitch, a pitch or offset that is no multiple of 4 halves (8 for a convolution's input), a misaligned buffer (16 bytes for
+ * convolution inputs, weights and biases, 8 for outputs and residuals), an output that overlaps its input, a residual that overlaps the
+ * output without being its window, a coarser level that overlaps the output or an odd output map with one, a photo outside `src`,
+ * a slot outside the batch, priors outside P.  VSP_ENOTSUP: a tensor of 2 GiB or more.  B = 0 (n = 0) returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_DET50_RELU 1               /* conv flags */
+
+int vsp_det50_stem_u8(void* y, const uint8_t* src, size_t src_bytes, const vsp_det_src* items, const vsp_det_src* items_dev, int n,
+                      const float* w, const float* b, int B, int Hc, int Wc, vsp_stream_t stream);
+int vsp_det50_pool_f16(void* y, const void* x, int B, int H, int W, int C, vsp_stream_t stream);
+int vsp_det50_conv_f16(void* y, int y_pitch, int y_off, const void* x, int x_pitch, int x_off, int B, int H, int W, int Cin, int Cout,
+                       int ksize, int stride, int flags, const void* w_img, const float* b, const void* res, int res_pitch, int res_off,
+                       const void* up, int up_pitch, int up_off, vsp_stream_t stream);
+int vsp_det50_heads_f32(float* conf, float* loc, float* lm, const void* x, int x_pitch, const float* w, const float* b, int B, int H, int W,
+                        int P, int p0, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

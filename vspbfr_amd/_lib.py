@@ -253,7 +253,11 @@ SIGNATURES = {
     "vsp_rrdb_head_u8": [_p, _i, _p, C.c_size_t, C.c_int64, _i, _i, _i, _i, _i, _p, _p, _p],
     "vsp_rrdb_conv_f16": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _i, _f, _p],
     "vsp_rrdb_tail_u8": [_p, C.c_size_t, C.c_int64, C.c_int64, _i, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
-    "vsp_fid_stem_u8": [_p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p, _p, _p],
+    "vsp_det50_stem_u8": [_p, _p, C.c_size_t, _p, _p, _i, _p, _p, _i, _i, _i, _p],
+    "vsp_det50_pool_f16": [_p, _p, _i, _i, _i, _i, _p],
+    "vsp_det50_conv_f16": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _p],
+    "vsp_det50_heads_f32": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p],
+    "vsp_fid_stem_u8":[_p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "vsp_fid_conv_f32": [_p, _p, _p, _p] + [_i] * 13 + [_p],
     "vsp_fid_pool_f32": [_p, _p] + [_i] * 8 + [_p],
 }

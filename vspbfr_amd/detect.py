@@ -1,4 +1,5 @@
 """Face detection for whole photos: RetinaFace with the MobileNet-0.25 backbone on the device, the host side of csrc/detect.hip.
+A checkpoint of the ResNet-50 network goes to vspbfr_amd.detect_r50: load_detector chooses by key.
 
     python -m vspbfr_amd.detect --photos DIR --weights W --out landmarks.json [--threshold 0.8] [--nms 0.4] [--side 1024]
         [--max_faces N] [--min_face PX]
@@ -10,6 +11,7 @@ digits that give back its float32 value.
     expected_state / check_state_dict   the key layout of the public `mobilenet0.25` RetinaFace checkpoint (300 entries) and the loader's rules
     fold_state                          BatchNorm folded into weight and bias in float64, in the kernels' layouts
     RetinaFaceDetector                  weights -> network(), postprocess(), detect()
+    load_detector                       a file with `body.layer1.0.conv1.weight` -> detect_r50.RetinaFaceR50Detector, any other -> RetinaFaceDetector
     write_landmarks / format_f32        the JSON writer
 
 No weights are shipped.  The key layout is written from the public model definition and could not be checked against a real checkpoint
@@ -78,9 +80,10 @@ def expected_state(with_tracked=True):
     return out
 
 
-def check_state_dict(sd):
+def check_state_dict(sd, want=None, what="RetinaFace mobilenet0.25 checkpoint"):
     """The loader's rules: a leading `module.` is stripped from every key, `num_batches_tracked` entries are ignored, any other missing or
-    unexpected key and any wrong shape is a ValueError that names it -> {key: float64 CPU tensor}"""
+    unexpected key and any wrong shape is a ValueError that names it -> {key: float64 CPU tensor}.  want: {key: shape} without the
+    BatchNorm counters (this module's expected_state by default), `what` the name of the checkpoint in the messages."""
     if isinstance(sd, dict) and "state_dict" in sd and not any(str(k).endswith(".weight") for k in sd):
         sd = sd["state_dict"]
     clean = {}
@@ -88,16 +91,16 @@ def check_state_dict(sd):
         k = k[len("module."):] if k.startswith("module.") else k
         if not k.endswith("num_batches_tracked"):
             clean[k] = v
-    want = expected_state(with_tracked=False)
+    want = expected_state(with_tracked=False) if want is None else want
     missing, extra = sorted(set(want) - set(clean)), sorted(set(clean) - set(want))
     if missing or extra:
-        raise ValueError("RetinaFace mobilenet0.25 checkpoint: " + "; ".join(
+        raise ValueError(what + ": " + "; ".join(
             f"{what} {', '.join(ks[:8])}{' ...' if len(ks) > 8 else ''}" for what, ks in (("missing keys", missing), ("unexpected keys", extra)) if ks))
     out = {}
     for k, shape in want.items():
         t = torch.as_tensor(clean[k]).detach().to("cpu", torch.float64)
         if tuple(t.shape) != tuple(shape):
-            raise ValueError(f"RetinaFace mobilenet0.25 checkpoint: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+            raise ValueError(f"{what}: {k} has shape {tuple(t.shape)}, expected {tuple(shape)}")
         out[k] = t
     return out
 
@@ -328,6 +331,21 @@ class RetinaFaceDetector:
         return out
 
 
+def load_detector(weights, device):
+    """weights: a path (torch.load) or a state dict -> the detector for it: a checkpoint that holds `body.layer1.0.conv1.weight` (after the
+    loader's `module.` stripping) is RetinaFace's ResNet-50 network and goes to detect_r50.RetinaFaceR50Detector, anything else to
+    RetinaFaceDetector, whose loader accepts or refuses it as before."""
+    if isinstance(weights, (str, os.PathLike)):
+        weights = torch.load(weights, map_location="cpu")
+    sd = weights
+    if isinstance(sd, dict) and "state_dict" in sd and not any(str(k).endswith(".weight") for k in sd):
+        sd = sd["state_dict"]
+    if isinstance(sd, dict) and any(str(k) in ("body.layer1.0.conv1.weight", "module.body.layer1.0.conv1.weight") for k in sd):
+        from .detect_r50 import RetinaFaceR50Detector
+        return RetinaFaceR50Detector(weights, device)
+    return RetinaFaceDetector(weights, device)
+
+
 def add_detect_arguments(ap, prefix=""):
     """the five detection options of both CLIs (`prefix` = "detect_" in restore_photos)"""
     ap.add_argument(f"--{prefix}threshold", type=float, default=DEFAULT_THRESHOLD, help="score above which a prior is a candidate")
@@ -355,7 +373,7 @@ def check_detect_arguments(threshold, nms, side, max_faces, min_face):
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Detect faces in photos and write the landmarks file of vspbfr_amd.restore_photos")
     ap.add_argument("--photos", type=str, required=True, help="directory of photos (searched recursively)")
-    ap.add_argument("--weights", type=str, required=True, help="RetinaFace mobilenet0.25 checkpoint (not shipped)")
+    ap.add_argument("--weights", type=str, required=True, help="RetinaFace checkpoint, mobilenet0.25 or resnet50 (not shipped)")
     ap.add_argument("--out", type=str, required=True, help="the landmarks JSON to write")
     add_detect_arguments(ap)
     args = ap.parse_args(argv)
@@ -370,7 +388,7 @@ def main(argv=None):
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(device)
     try:
-        det = RetinaFaceDetector(args.weights, device)
+        det = load_detector(args.weights, device)
     except ValueError as e:
         ap.error(str(e))
     found = {}

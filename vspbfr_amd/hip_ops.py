@@ -2507,11 +2507,89 @@ def rrdb_tail_u8(out, out_off, out_pitch, out_w, info, x, x_pitch, H, W, keep0, 
     return out
 
 
+# --------------------------------------------------------------------------------- face detection, ResNet-50
+DET50_RELU = 1      # include/vspbfr_hip.h VSP_DET50_RELU
+
+
+def _det50_act(t, name, need):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float16 or t.dim() != 1 or not t.is_contiguous() or t.numel() < need:
+        raise RuntimeError(f"{name} must be a flat contiguous CUDA float16 tensor of at least {need} elements")
+    return t
+
+
+def det50_out_size(H, W, stride):
+    """(OH, OW) of a convolution of vsp_det50_conv_f16 (1x1 without, 3x3 with padding 1) and of the stem and the pool at stride 2"""
+    return (int(H) - 1) // int(stride) + 1, (int(W) - 1) // int(stride) + 1
+
+
+def det50_stem_u8(y, src, items, items_dev, n, w, b, B, Hc, Wc):
+    """The ResNet-50 detector's stem on n u8 photos inside `src` (vsp_det50_stem_u8): writes images `slot` of y, a flat float16 buffer
+    holding (B, ceil(Hc/2), ceil(Wc/2), 64), for the items of `items` (a _lib.DetSrc array; items_dev the same bytes on the device).
+    w (147, 64), b (64) float32.  Returns y."""
+    _u8(src, "src"), _u8(items_dev, "items_dev"), _req(w, "w"), _req(b, "b")
+    B, Hc, Wc = int(B), int(Hc), int(Wc)
+    oh, ow = det50_out_size(Hc, Wc, 2)
+    _det50_act(y, "y", B * oh * ow * 64)
+    if w.numel() != 147 * 64 or b.numel() != 64:
+        raise RuntimeError(f"det50_stem_u8: w {tuple(w.shape)}, b {tuple(b.shape)}")
+    if items_dev.numel() < n * C.sizeof(_lib.DetSrc):
+        raise RuntimeError("det50_stem_u8: items_dev is shorter than the item table")
+    check(lib.vsp_det50_stem_u8(_ptr(y), _ptr(src), src.numel(), C.cast(items, C.c_void_p), _ptr(items_dev), int(n), _ptr(w), _ptr(b), B, Hc,
+                                Wc, _stream()), "det50_stem_u8")
+    return y
+
+
+def det50_pool_f16(y, x, B, H, W, C_):
+    """3x3 / 2 / pad 1 max pool (vsp_det50_pool_f16): x holds (B, H, W, C_) float16, y takes (B, ceil(H/2), ceil(W/2), C_).  Returns y."""
+    B, H, W, C_ = int(B), int(H), int(W), int(C_)
+    oh, ow = det50_out_size(H, W, 2)
+    _det50_act(x, "x", B * H * W * C_), _det50_act(y, "y", B * oh * ow * C_)
+    check(lib.vsp_det50_pool_f16(_ptr(y), _ptr(x), B, H, W, C_, _stream()), "det50_pool_f16")
+    return y
+
+
+def det50_conv_f16(y, y_pitch, y_off, x, x_pitch, x_off, B, H, W, w_img, b, stride=1, relu=False, res=None, up=None):
+    """One convolution of the ResNet-50 detector (vsp_det50_conv_f16): channels x_off .. x_off + Cin - 1 of x, a flat float16 buffer
+    holding (B, H, W, x_pitch), -> channels y_off .. y_off + Cout - 1 of y, (B, OH, OW, y_pitch), as f16([relu](conv + b [+ res]) [+ up]).
+    The filter (1x1, or 3x3 with padding 1) and the channel counts come from w_img, detect_r50.pack_conv_weight's image
+    (taps, Cin / 32, Cout / 16, 64, 8); b float32 (Cout).  res: None or (flat float16 tensor, pitch, offset) at the output's size, which may
+    be y's own window; up: None or (tensor, pitch, offset) of an (OH / 2, OW / 2) map read at (oy >> 1, ox >> 1).  Returns y."""
+    B, H, W, y_pitch, y_off, x_pitch, x_off, stride = (int(v) for v in (B, H, W, y_pitch, y_off, x_pitch, x_off, stride))
+    if not isinstance(w_img, torch.Tensor) or not w_img.is_cuda or w_img.dtype != torch.float16 or not w_img.is_contiguous() or w_img.dim() != 5 \
+            or tuple(w_img.shape[3:]) != (64, 8) or int(w_img.shape[0]) not in (1, 9):
+        raise RuntimeError("det50_conv_f16: w_img must be a contiguous CUDA float16 image (1 | 9, Cin / 32, Cout / 16, 64, 8)")
+    ks, cin, cout = (1 if int(w_img.shape[0]) == 1 else 3), 32 * int(w_img.shape[1]), 16 * int(w_img.shape[2])
+    _req(b, "b")
+    if b.numel() != cout:
+        raise RuntimeError(f"det50_conv_f16: {b.numel()} biases for {cout} channels")
+    oh, ow = det50_out_size(H, W, stride) if stride in (1, 2) else (H, W)
+    _det50_act(x, "x", B * H * W * x_pitch), _det50_act(y, "y", B * oh * ow * y_pitch)
+    r = [None, 0, 0] if res is None else [_ptr(_det50_act(res[0], "res", B * oh * ow * int(res[1]))), int(res[1]), int(res[2])]
+    u = [None, 0, 0] if up is None else [_ptr(_det50_act(up[0], "up", B * (oh // 2) * (ow // 2) * int(up[1]))), int(up[1]), int(up[2])]
+    check(lib.vsp_det50_conv_f16(_ptr(y), y_pitch, y_off, _ptr(x), x_pitch, x_off, B, H, W, cin, cout, ks, stride, DET50_RELU if relu else 0,
+                                 _ptr(w_img), _ptr(b), r[0], r[1], r[2], u[0], u[1], u[2], _stream()), "det50_conv_f16")
+    return y
+
+
+def det50_heads(x, x_pitch, B, H, W, w, b, conf, loc, lm, p0):
+    """The class, box and landmark heads of one level (vsp_det50_heads_f32): channels 0 .. 255 of x, a flat float16 buffer holding
+    (B, H, W, x_pitch); w (256, 32), b (32) float32 -> priors p0 .. p0 + 2 H W - 1 of conf (B, P, 2), loc (B, P, 4), lm (B, P, 10)."""
+    for t, nm in ((w, "w"), (b, "b"), (conf, "conf"), (loc, "loc"), (lm, "lm")):
+        _req(t, nm)
+    B, H, W, x_pitch = int(B), int(H), int(W), int(x_pitch)
+    _det50_act(x, "x", B * H * W * x_pitch)
+    P = int(conf.shape[1]) if conf.dim() == 3 else -1
+    if tuple(w.shape) != (256, 32) or tuple(b.shape) != (32,) or tuple(conf.shape) != (B, P, 2) or tuple(loc.shape) != (B, P, 4) \
+            or tuple(lm.shape) != (B, P, 10):
+        raise RuntimeError(f"det50_heads: w {tuple(w.shape)}, conf {tuple(conf.shape)}, loc {tuple(loc.shape)}, lm {tuple(lm.shape)} for a batch of {B}")
+    check(lib.vsp_det50_heads_f32(_ptr(conf), _ptr(loc), _ptr(lm), _ptr(x), x_pitch, _ptr(w), _ptr(b), B, H, W, P, int(p0), _stream()), "det50_heads")
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types
     skip = {"conv_key", "conv_route", "fir_out_size", "fir_bf16_ok", "conv2d_out_size", "operand_device", "device_guarded", "check", "parse_conv_out",
-            "fid_conv_out", "fid_pool_out"}
+            "fid_conv_out", "fid_pool_out", "det50_out_size"}
     g = globals()
     for name, obj in list(g.items()):
         if isinstance(obj, types.FunctionType) and not name.startswith("_") and name not in skip and obj.__module__ == __name__:

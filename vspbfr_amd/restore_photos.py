@@ -48,8 +48,10 @@ the --save_faces files through the uniform encoder (vsp_png_encode_u8).  The fil
 from Pillow's, as any two PNG encoders' do.  report.json then lists `png_encode`.  With --format jpg the flag needs --save_faces (no
 other file is a PNG).  Default host: Pillow, nothing changes.
 
---detect_weights W: the faces are found on the device by RetinaFace / MobileNet-0.25 (vspbfr_amd.detect, csrc/detect.hip) from
-the checkpoint W -- no weights are shipped, and the key layout the loader expects is unverified against a real file.  Every group of
+--detect_weights W: the faces are found on the device by RetinaFace from the checkpoint W: the MobileNet-0.25 network (vspbfr_amd.detect,
+csrc/detect.hip) or, for a file that holds `body.layer1.0.conv1.weight`, the ResNet-50 network (vspbfr_amd.detect_r50,
+csrc/detect_r50.hip; report.json's `detect` then lists `backbone`) -- no weights are shipped, and the key layouts the loaders
+expect are unverified against a real file.  Every group of
 photos goes through one detect() call (with --decode device on the decoder's buffer); a detected face that the validation of --landmarks
 would refuse (degenerate landmarks, with --antialias a minification above 16) is dropped and listed with its reason.  report.json then
 lists `detect` (the parameters) and per photo `score`, `box` and, if any, `dropped`; OUT/landmarks.json (landmarks_<rank>.json in a
@@ -82,7 +84,7 @@ import os
 import numpy as np
 import torch
 
-from .detect import RetinaFaceDetector, add_detect_arguments, check_detect_arguments
+from .detect import add_detect_arguments, check_detect_arguments, load_detector
 from .e4e import E4e_embedding
 from .imageio import JpegWriter, PngWriter, list_images
 from .photo import DEFAULT_FEATHER, DEFAULT_INSET, PhotoRestorer, check_color_fix, check_minify, similarity_from_landmarks
@@ -136,6 +138,12 @@ def _groups(names, landmarks, batch):
 def list_photos(root):
     """the photos under `root` as sorted paths relative to it"""
     return [os.path.relpath(p, root) for p in list_images(root)]
+
+
+def detect_report(detector, detect_params):
+    """report.json's `detect` entry: the parameters, and `backbone` for a detector that names one (the ResNet-50 route alone)"""
+    backbone = getattr(detector, "backbone", None)
+    return dict(detect_params, backbone=backbone) if backbone else detect_params
 
 
 def detect_group(detector, params, group, landmarks, found, photos=None, device_photos=None, size=512, upscale=1, antialias=False):
@@ -260,7 +268,7 @@ def restore_photos(args, restorer, names, landmarks, device, rank=0, world=1, de
             print("warning: non-finite parsing logits (those pixels are class 0 and keep the photo) in: " + ", ".join(parse_nonfinite))
     if detector is not None:
         from .detect import write_landmarks
-        head.update(detect=detect_params)
+        head.update(detect=detect_report(detector, detect_params))
         write_landmarks(os.path.join(args.out, "landmarks.json" if world == 1 else "landmarks_%d.json" % rank),
                         {n: landmarks[n] for n in names[lo:hi] if landmarks.get(n)})
     with open(os.path.join(args.out, name), "w") as f:
@@ -285,7 +293,7 @@ def main(argv=None):
     ap.add_argument("--photos", type=str, required=True, help="directory of photos (searched recursively)")
     ap.add_argument("--landmarks", type=str, default=None, help='JSON: {"relative/name.png": [[[x, y] x 5], ...one entry per face]}')
     ap.add_argument("--detect_weights", type=str, default=None,
-                    help="RetinaFace mobilenet0.25 checkpoint (not shipped): find the faces on the device instead of reading --landmarks")
+                    help="RetinaFace checkpoint, mobilenet0.25 or resnet50 (not shipped): find the faces on the device instead of reading --landmarks")
     add_detect_arguments(ap, "detect_")
     ap.add_argument("--out", type=str, required=True, help="output directory")
     ap.add_argument("--upscale", type=int, choices=[1, 2, 4], default=1, help="resize the photo (Pillow LANCZOS) and paste the faces at that scale")
@@ -387,7 +395,7 @@ def main(argv=None):
     detector = None
     if args.detect_weights is not None:
         try:
-            detector = RetinaFaceDetector(args.detect_weights, device)
+            detector = load_detector(args.detect_weights, device)
         except ValueError as e:
             ap.error(str(e))
     restore_photos(args, restorer, names, landmarks, device, rank, world, detector, detect_params)
