@@ -86,10 +86,13 @@ typedef struct vsp_fir_epilogue {
   int act;                  /* 0 none, 1 leaky-relu */
   float slope;              /* 0.2 */
   float gain;               /* sqrt(2) */
-  int flags;                /* VSP_FIR_SEPARABLE: kernel[ky][kx] == kernel[ky][0] * kernel[0][kx] / kernel[0][0] (an outer product, as every
-                             * blur of the path is: make_kernel([1,3,3,1]), models/RestoreNet.py:38-48) -- the caller's promise; the blur
-                             * kernels may then run a row pass and a column pass (8 multiply-adds per output instead of 16); the result
-                             * differs from the 2-D form by rounding only.  0 = general taps. */
+  int flags;                /* VSP_FIR_SEPARABLE: the LAST tap is not zero, kernel[kh-1][kw-1] != 0, and
+                             *   kernel[ky][kx] == kernel[ky][kw-1] * kernel[kh-1][kx] / kernel[kh-1][kw-1]   for every ky, kx
+                             * (an outer product written with its last row and column, as every blur of the path is: make_kernel([1,3,3,1]),
+                             * models/RestoreNet.py:38-48) -- the caller's promise.  The kernels work on the flipped taps and DIVIDE by that
+                             * corner: an outer product whose last tap is zero (outer([1,3,3,0], .)) must not be flagged.  The blur kernels
+                             * may then run a row pass and a column pass (8 multiply-adds per output instead of 16); the result differs from
+                             * the 2-D form by rounding only.  0 = general taps. */
 } vsp_fir_epilogue;
 #define VSP_FIR_SEPARABLE 1
 

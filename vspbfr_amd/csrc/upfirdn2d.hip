@@ -547,7 +547,9 @@ static int upfirdn2d_impl(T* out, const T* x, const float* kernel, int major, in
     e.enabled = (e.plane_scale || e.noise || e.act || e.res1 || e.res2) ? 1 : 0;
   }
   hipStream_t s = vsp::as_stream(stream);
-  const bool tile_ok = (up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && minor == 1 && out_w >= 16);
+  // in_w >= 4, in_h >= 1: the tile kernel's window loader fetches four elements at a column clamped to [0, in_w - 4] of a row clamped to
+  // [0, in_h - 1] -- a narrower (or empty) plane under wide pads would put that address before the tensor's first byte
+  const bool tile_ok = (up_x == 1 && up_y == 1 && down_x == 1 && down_y == 1 && minor == 1 && out_w >= 16 && in_w >= 4 && in_h >= 1);
   // (fp32 planes stay on the tile kernel: the same strip walk measured 4.6 against 4.2 TB/s on 32 channels at 1024^2 but 3.4-4.0 against
   //  4.1-4.6 everywhere else -- 151 registers, three waves per SIMD, twice the bytes per lane in flight; default bench 195.6 against 195.1)
   if constexpr (BF) {
@@ -556,7 +558,15 @@ static int upfirdn2d_impl(T* out, const T* x, const float* kernel, int major, in
     const int64_t xb = (int64_t)major * in_h * in_w * 2, ob = (int64_t)major * out_h * out_w * 2;
     // rows that are not whole strips (the down-sampling blurs: 2^n + 1 outputs per row): whole strips + a TAIL launch, plain form only
     const bool ragged = out_w % 8 != 0;
+    // pad_x0 <= in_h * in_w: a row of plane 1 starts in_h * in_w elements into the tensor at the least, and the strip's first load lies pad_x0
+    // elements before it -- a larger left pad (planes of a few pixels) makes that offset negative, which the range check answers with zeros for
+    // the WHOLE load, its valid columns included.
+    // in_w + pad_x0 even: the range check works on dwords.  The loads of the tensor's LAST row start at element (major in_h - 1) in_w + ox -
+    // pad_x0 (ox even); when that differs in parity from the element count major in_h in_w, i.e. when in_w + pad_x0 is odd, one dword of the
+    // row holds the tensor's last element in its low half and two bytes past the end in its high half -- out of range, so the last element
+    // reads as zero and the outputs under it are wrong (every blur of the path has an even sum: 2H + 1 with pad 1, 2H with pad 2).
     if (strip_env && tile_ok && kh == 4 && kw == 4 && (!ragged || !e.enabled) && out_h >= 4 && xb < 0x7ffffff0ll && ob < 0x7ffffff0ll &&
+        pad_x0 <= (int64_t)in_h * in_w && ((in_w + pad_x0) & 1) == 0 &&
         (ragged || (reinterpret_cast<uintptr_t>(out) & 15) == 0) && (!e.res1 || (reinterpret_cast<uintptr_t>(e.res1) & 15) == 0) &&
         (!e.res2 || (reinterpret_cast<uintptr_t>(e.res2) & 15) == 0) && (!e.noise || (reinterpret_cast<uintptr_t>(e.noise) & 15) == 0)) {
       constexpr int RC = VSP_STRIP_RC;
@@ -626,7 +636,7 @@ static int upfirdn2d_impl(T* out, const T* x, const float* kernel, int major, in
     return vsp::check_launch("upfirdn2d(tile)");
   }
   if constexpr (BF) {
-    return vsp::fail(VSP_ENOTSUP, "upfirdn2d_bf16: only the blur form (up = down = 1, minor = 1, 2x2 / 3x3 / 4x4 taps, width >= 16) has a bf16 kernel");
+    return vsp::fail(VSP_ENOTSUP, "upfirdn2d_bf16: only the blur form (up = down = 1, minor = 1, 2x2 / 3x3 / 4x4 taps, output width >= 16, input width >= 4) has a bf16 kernel");
   } else {
     int64_t blocks = (total + 255) / 256;
     if (blocks > vsp::kMaxStreamBlocks) blocks = vsp::kMaxStreamBlocks;

@@ -270,9 +270,9 @@ def upfirdn2d_native_layout(input, kernel, up_x, up_y, down_x, down_y, pad_x0, p
     return out
 
 
-def fir_bf16_ok(kh, kw, up, down, minor, out_w):
-    """What vsp_upfirdn2d_bf16 serves: the blur form."""
-    return up == 1 and down == 1 and minor == 1 and out_w >= 16 and (kh, kw) in ((4, 4), (3, 3), (2, 2))
+def fir_bf16_ok(kh, kw, up, down, minor, out_w, in_w=4, in_h=1):
+    """What vsp_upfirdn2d_bf16 serves: the blur form on planes of at least 1 x 4 pixels (narrower ones under wide pads: fp32, generic kernel)."""
+    return up == 1 and down == 1 and minor == 1 and out_w >= 16 and in_w >= 4 and in_h >= 1 and (kh, kw) in ((4, 4), (3, 3), (2, 2))
 
 
 SEPARABLE_BLUR = tune_env("VSP_FIR_SEPARABLE", "1") != "0"   # (A/B runs: the 2-D form)
@@ -305,7 +305,7 @@ def blur_fused(x, kernel, pad, plane_scale=None, noise=None, noise_w=None, act_b
     x = _req(x, "x", bf16_ok=True)
     B, Cc, H, W = x.shape
     kh, kw = kernel.shape
-    if x.dtype == BF and not fir_bf16_ok(kh, kw, 1, 1, 1, fir_out_size(H, W, kh, kw, 1, 1, 1, 1, pad[0], pad[1], pad[0], pad[1])[1]):
+    if x.dtype == BF and not fir_bf16_ok(kh, kw, 1, 1, 1, fir_out_size(H, W, kh, kw, 1, 1, 1, 1, pad[0], pad[1], pad[0], pad[1])[1], W, H):
         x = to_f32(x)
     res1, res2 = as_dtype(res1, x.dtype), as_dtype(res2, x.dtype)
     epi = FirEpilogue()
