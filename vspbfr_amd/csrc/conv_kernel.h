@@ -297,7 +297,12 @@ __global__ __launch_bounds__(64 * WM * WN * WK, OCC) void conv_igemm_kernel(cons
         const int tap = row / CK, cl = row - tap * CK;
         const int ci = ci0 + cl;
         float v = 0.f;
-        if (ci < p.Cin && co0 + c < p.cout_g) v = wg[((int64_t)tap * p.Cin + ci) * p.cout_g + co0 + c];
+        if constexpr (DG) {  // slab column block c >> 4 = group, 16 channels co0.. of each (as in woff above)
+          const int cc = co0 + (c & 15);
+          if (ci < p.Cin && cc < p.cout_g) v = wg[(((int64_t)(c >> 4) * T + tap) * p.Cin + ci) * p.cout_g + cc];
+        } else {
+          if (ci < p.Cin && co0 + c < p.cout_g) v = wg[((int64_t)tap * p.Cin + ci) * p.cout_g + co0 + c];
+        }
         Wl[row * WS + c] = v;
       }
     }
