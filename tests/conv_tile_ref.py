@@ -188,19 +188,22 @@ def operands(case):
     ch, tr, tg = case.chain, case.transposed, case.x_gs > 0
     o = dict(in_scale=None, in_shift=False, out_scale=False, ch_scale=False, ch_bias=False, act1=False, noise=False, act2=0, bias2=False,
              slope2=0.2, gain2=SQRT2, res=0, res_coff=0, res_pad=0, y_coff=0, y_pad=0, os=(1, 1), oo=(0, 0))
-    if ch == "style":
+    if ch in ("style", "stylefp"):      # (stylefp: tests/conv_bf16_ref.py, the style chain with scales of full fp32 precision)
         o.update(in_scale="sample", out_scale=True, act1=True, act2=1, bias2=True)
         if not tr:
             o.update(noise=True, res=2, res_coff=2, res_pad=3)
+    elif ch == "demod":     # (tests/conv_bf16_ref.py: what a modulated layer without activation hands over -- style, demodulation, scale and bias)
+        o.update(in_scale="sample", out_scale=True, ch_scale=True, ch_bias=True)
     elif ch == "bn":
         o.update(in_scale="channel", in_shift=not tg, ch_scale=True, ch_bias=True, act2=2, bias2=True)
     elif ch in SLOPES:
         o.update(act2=1, bias2=True, slope2=SLOPES[ch], gain2=1.0)
-    elif ch in ("place", "placexy"):
+    elif ch in ("place", "placexy", "placed"):
         o.update(y_coff=3, y_pad=5)
         if not tr:
             o.update(noise=True, res=1, res_coff=1, res_pad=2)
-            o.update(os=(2, 2), oo=(1, 1)) if ch == "place" else o.update(os=(1, 2), oo=(1, 0))
+            if ch != "placed":      # "placed" (tests/conv_bf16_ref.py: entries with a dense output only) keeps the unit lattice
+                o.update(os=(2, 2), oo=(1, 1)) if ch == "place" else o.update(os=(1, 2), oo=(1, 0))
     return o
 
 
@@ -329,12 +332,14 @@ def _accumulate(case, d, dtype, wrong):
     return acc
 
 
-def reference(case, d, dtype, wrong=None):
+def reference(case, d, dtype, wrong=None, acc=None):
     """-> y [B, y_ch, y_h, y_w] in `dtype`: the contract's value where the launch writes, SENTINEL everywhere else.
-    wrong: one of WRONG_VARIANTS (a plausible mistake, for the CPU test of the inputs), None = the contract."""
+    wrong: one of WRONG_VARIANTS (a plausible mistake, for the CPU test of the inputs), None = the contract.
+    acc: the accumulators [B, Cout, OH, OW] when the caller has summed them itself (tests/conv_bf16_ref.py: operands rounded where the
+    bf16 kernels round them); the epilogue chain and the placement are then applied to it."""
     o, g = operands(case), geom(case)
     B = case.B
-    v = _accumulate(case, d, dtype, wrong)
+    v = _accumulate(case, d, dtype, wrong) if acc is None else acc.to(dtype)
     ch = lambda k: d[k].to(dtype)[None, :, None, None]       # noqa: E731
     if "out_scale" in d:
         v = v * d["out_scale"].to(dtype)[:, :, None, None]
@@ -356,8 +361,27 @@ def reference(case, d, dtype, wrong=None):
         v = _lrelu(v + ch("bias1"), 0.2) * SQRT2
     if nz is not None and wrong != "noise_before_act1":
         v = v + nz
+    (osy, osx), (ooy, oox) = g.os, g.oo
+    if wrong == "offset_swap":
+        ooy, oox = oox, ooy
+    rows = slice(ooy, ooy + (g.OH - 1) * osy + 1, osy)
+    cols = slice(oox, oox + (g.OW - 1) * osx + 1, osx)
+
+    def add_res(v):
+        for k in ("res1", "res2"):
+            if k in d:
+                rc = 0 if wrong == "res_coff_ignored" else g.res_coff
+                v = v + d[k].to(dtype)[:, rc:rc + g.Cout, rows, cols]      # the residual has the layout of the written region
+        return v
+
+    # (two mistakes that only tests/conv_bf16_ref.py draws: the residuals added before the second activation, bias2 added after it)
+    if wrong == "res_before_act2" and not case.transposed:
+        v = add_res(v)
     if o["act2"] == 1:
-        v = _lrelu(v if wrong == "bias2_dropped" else v + ch("bias2"), o["slope2"]) * o["gain2"]
+        if wrong == "bias2_after_act":
+            v = _lrelu(v, o["slope2"]) * o["gain2"] + ch("bias2")
+        else:
+            v = _lrelu(v if wrong == "bias2_dropped" else v + ch("bias2"), o["slope2"]) * o["gain2"]
     elif o["act2"] == 2:
         if wrong == "bias2_with_prelu":
             v = v + ch("bias2")
@@ -372,15 +396,8 @@ def reference(case, d, dtype, wrong=None):
         else:
             win.copy_(v)
         return y
-    (osy, osx), (ooy, oox) = g.os, g.oo
-    if wrong == "offset_swap":
-        ooy, oox = oox, ooy
-    rows = slice(ooy, ooy + (g.OH - 1) * osy + 1, osy)
-    cols = slice(oox, oox + (g.OW - 1) * osx + 1, osx)
-    for k in ("res1", "res2"):
-        if k in d:
-            rc = 0 if wrong == "res_coff_ignored" else g.res_coff
-            v = v + d[k].to(dtype)[:, rc:rc + g.Cout, rows, cols]      # the residual has the layout of the written region
+    if wrong != "res_before_act2":
+        v = add_res(v)
     y[:, g.y_coff:g.y_coff + g.Cout, rows, cols] = v
     return y
 

@@ -264,7 +264,8 @@ __global__ __launch_bounds__(BNT, (MB == 1 && MODE == 0 && PT <= 3 && !SPLIT) ? 
   float pregA[PT][8], pregB[PT][8];
   // (NOSC: the descriptor ends with this group's last channel plane -- the range check compares the lane offset with size - scalar offset)
   const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<AT*>(xb), 0, NOSC ? p.Cin * chw * (int)ES : 0x7fffffff, 0x00020000);
-  const float* iscp = p.in_scale + (int64_t)b * p.in_scale_bstride;
+  // (true groups: in_scale has x_ch entries per image and group g reads them from g * x_gs on, as it reads x -- the header's contract)
+  const float* iscp = p.in_scale + (int64_t)b * p.in_scale_bstride + (int64_t)g * p.x_gs * p.bf_isc_s;
   const float* ishp = p.in_shift;
   // Cin is a multiple of 8 (host): a wave's channel octet is either wholly inside or wholly past Cin
   auto issue_p = [&](float (&pr)[PT][8], int c) {
