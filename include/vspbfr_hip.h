@@ -1433,6 +1433,43 @@ int vsp_det50_conv_f16(void* y, int y_pitch, int y_off, const void* x, int x_pit
 int vsp_det50_heads_f32(float* conf, float* loc, float* lm, const void* x, int x_pitch, const float* w, const float* b, int B, int H, int W,
                         int P, int p0, vsp_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Facial landmarks with face_alignment's 2D-FAN (csrc/fan.hip): f16 operands, fp32 accumulation.  Activations are
+ * (B, H, W, pitch) _Float16: a tensor is a pointer, a channel pitch and a channel offset.
+ *   stem    y = f16(relu(conv7x7/2/pad3(crop) + b)), 3 -> 64 in fp32 fmaf; crop = the box (x0, y0, s) of box[3 b ..] of photo b of src,
+ *           (B, H, W, 3) u8 RGB, sampled to side x side bilinearly at half-pixel centres without anti-aliasing, 0 outside the photo,
+ *           divided by 255; it is never stored.  y is (B, side / 2, side / 2, 64).  w (147, 64) fp32, row (7 ky + kx) 3 + channel; b (64).
+ *   pool    2x2 mean, f16(((a + b) + (c + d)) / 4) in fp32, between channel windows; H and W even.
+ *   conv    v = conv(x') [+ b] [relu]; raw = f16(v) (optional); y = v [+ res1] [+ res2] [+ up], rounded once to f16 or, with
+ *           VSP_FAN_OUT_F32, stored as fp32 (pitch and offset then count floats).  x' = x, or with in_a / in_b (fp32, Cin each)
+ *           f16(max(fmaf(in_a[c], x, in_b[c]), 0)) -- a rounding point; a tap outside the map is 0 behind the affine.  ksize 1 or 3
+ *           (padding 1), stride 1.  Cin: a multiple of 32 up to 256 (a 68-channel input is a 96-channel window whose last 28 are zero).
+ *           Cout: a multiple of 32 up to 256, or 68.  res1 / res2 (ptr, pitch, offset) are read at the output pixel and may be the very
+ *           window written; up is an (H / 2, W / 2) map read at (y >> 1, x >> 1), H and W even.  One fixed order of the sum per output
+ *           pixel: an image's result depends neither on the batch size nor on its position in the batch.
+ *           w_img: f16 (ksize^2, Cin / 32, Cp / 16, 64, 8), Cp = Cout rounded up to 32 with zero rows: element j of lane l of block nb
+ *           of step kc of tap t = w[co = 16 nb + (l & 15)][ci = 32 kc + 8 (l >> 4) + j][ky = t / ksize][kx = t % ksize].  b: fp32 (Cout) or null.
+ *   decode  per (image, landmark k < K) of hm (B, n, n, pitch) fp32: argmax (lowest flat index among equals; a non-finite value is
+ *           flagged and never wins), lm = x0 + (px + 0.5 + dx) s / n with dx = 0.25 sign(hm[py][px + 1] - hm[py][px - 1]), 0 on the border
+ *           (the same in y), peak = the maximum, flag = 1 when the map holds a non-finite value.  lm (B, K, 2), peak (B, K), flag (B, K).
+ * VSP_EINVAL, nothing launched: a null pointer, a channel count, filter or flag that is not served, a channel window outside its
+ * pitch, a pitch or offset that is no multiple of 4 elements (8 for an input), a misaligned buffer (16 bytes for inputs, weights, biases,
+ * affines and fp32 outputs, 8 for f16 outputs and residuals), an output that overlaps its input or the other output, a residual that
+ * overlaps the output without being its window, a coarser level that overlaps an output, an odd map with a coarser level or in the pool.
+ * VSP_ENOTSUP: a tensor of 2 GiB or more.  B = 0 returns VSP_OK.
+ * ---------------------------------------------------------------------------------------------- */
+#define VSP_FAN_RELU 1                 /* conv flags */
+#define VSP_FAN_OUT_F32 2
+
+int vsp_fan_stem_u8(void* y, const uint8_t* src, const float* box, const float* w, const float* b, int B, int H, int W, int side,
+                    vsp_stream_t stream);
+int vsp_fan_pool_f16(void* y, int y_pitch, int y_off, const void* x, int x_pitch, int x_off, int B, int H, int W, int C, vsp_stream_t stream);
+int vsp_fan_conv_f16(void* y, int y_pitch, int y_off, void* raw, int raw_pitch, int raw_off, const void* x, int x_pitch, int x_off, int B, int H,
+                     int W, int Cin, int Cout, int ksize, int flags, const void* w_img, const float* b, const float* in_a, const float* in_b,
+                     const void* res1, int res1_pitch, int res1_off, const void* res2, int res2_pitch, int res2_off, const void* up, int up_pitch,
+                     int up_off, vsp_stream_t stream);
+int vsp_fan_decode_f32(float* lm, float* peak, int32_t* flag, const float* hm, int pitch, const float* box, int B, int n, int K, vsp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -257,6 +257,10 @@ SIGNATURES = {
     "vsp_det50_pool_f16": [_p, _p, _i, _i, _i, _i, _p],
     "vsp_det50_conv_f16": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _i, _p, _i, _i, _p],
     "vsp_det50_heads_f32": [_p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p],
+    "vsp_fan_stem_u8": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "vsp_fan_pool_f16": [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p],
+    "vsp_fan_conv_f16": [_p, _i, _i, _p, _i, _i, _p, _i, _i] + [_i] * 7 + [_p, _p, _p, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i, _p],
+    "vsp_fan_decode_f32": [_p, _p, _p, _p, _i, _p, _i, _i, _i, _p],
     "vsp_fid_stem_u8":[_p, _p, C.c_size_t, _p, _p, _i, _i, _i, _i, _p, _p, _p],
     "vsp_fid_conv_f32": [_p, _p, _p, _p] + [_i] * 13 + [_p],
     "vsp_fid_pool_f32": [_p, _p] + [_i] * 8 + [_p],

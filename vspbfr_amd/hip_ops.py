@@ -2585,6 +2585,87 @@ def det50_heads(x, x_pitch, B, H, W, w, b, conf, loc, lm, p0):
     check(lib.vsp_det50_heads_f32(_ptr(conf), _ptr(loc), _ptr(lm), _ptr(x), x_pitch, _ptr(w), _ptr(b), B, H, W, P, int(p0), _stream()), "det50_heads")
 
 
+# --------------------------------------------------------------------------------- facial landmarks, 2D-FAN
+FAN_RELU, FAN_OUT_F32 = 1, 2      # include/vspbfr_hip.h VSP_FAN_*
+
+
+def _fan_win(t, name, n_pix, what="float16"):
+    """(tensor, pitch, offset) -> [pointer, pitch, offset] of a channel window of a flat activation buffer; None -> [None, 0, 0]"""
+    if t is None:
+        return [None, 0, 0]
+    buf, pitch, off = t[0], int(t[1]), int(t[2])
+    dt = torch.float16 if what == "float16" else torch.float32
+    if not isinstance(buf, torch.Tensor) or not buf.is_cuda or buf.dtype != dt or buf.dim() != 1 or not buf.is_contiguous() or buf.numel() < n_pix * pitch:
+        raise RuntimeError(f"{name} must be a flat contiguous CUDA {what} tensor of at least {n_pix * pitch} elements")
+    return [_ptr(buf), pitch, off]
+
+
+def fan_stem_u8(y, src, box, w, b, side):
+    """2D-FAN's stem on the boxes of B u8 photos (vsp_fan_stem_u8): src (B, H, W, 3) uint8, box (B, 3) float32 (x0, y0, s) ->
+    y, a flat float16 buffer holding (B, side / 2, side / 2, 64).  w (147, 64), b (64) float32.  Returns y."""
+    _u8(src, "src"), _req(box, "box"), _req(w, "w"), _req(b, "b")
+    if src.dim() != 4 or src.shape[3] != 3 or not src.is_contiguous():
+        raise RuntimeError(f"fan_stem_u8: src must be a contiguous (B, H, W, 3) uint8 tensor (got {tuple(src.shape)})")
+    B, Hh, Ww, side = int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), int(side)
+    if tuple(box.shape) != (B, 3) or w.numel() != 147 * 64 or b.numel() != 64:
+        raise RuntimeError(f"fan_stem_u8: box {tuple(box.shape)} for a batch of {B}, w {tuple(w.shape)}, b {tuple(b.shape)}")
+    _det50_act(y, "y", B * (side // 2) * (side // 2) * 64)
+    check(lib.vsp_fan_stem_u8(_ptr(y), _ptr(src), _ptr(box), _ptr(w), _ptr(b), B, Hh, Ww, side, _stream()), "fan_stem_u8")
+    return y
+
+
+def fan_pool_f16(y, x, B, H, W, C_):
+    """2 x 2 mean (vsp_fan_pool_f16): channels of x = (flat float16 tensor, pitch, offset) holding (B, H, W, pitch) -> the window y of a
+    (B, H / 2, W / 2, pitch) buffer, C_ channels.  Returns y's tensor."""
+    B, H, W, C_ = int(B), int(H), int(W), int(C_)
+    xs, ys = _fan_win(x, "x", B * H * W), _fan_win(y, "y", B * (H // 2) * (W // 2))
+    check(lib.vsp_fan_pool_f16(ys[0], ys[1], ys[2], xs[0], xs[1], xs[2], B, H, W, C_, _stream()), "fan_pool_f16")
+    return y[0]
+
+
+def fan_conv_f16(y, x, B, H, W, w_img, cout, b=None, affine=None, relu=False, raw=None, res1=None, res2=None, up=None, out_f32=False):
+    """One convolution of 2D-FAN (vsp_fan_conv_f16).  x, y, raw, res1, res2, up: (flat tensor, pitch, offset) channel windows of
+    (B, H, W, pitch) buffers (up: (B, H / 2, W / 2, pitch)); all float16 except y with out_f32.  v = conv(x') [+ b] [relu], raw = f16(v),
+    y = v [+ res1] [+ res2] [+ up]; x' = f16(relu(a x + b')) with affine = (a, b') float32 (Cin each).  w_img: fan.pack_conv_weight's float16
+    image (1 | 9, Cin / 32, Cp / 16, 64, 8), Cp = cout rounded up to 32; b float32 (cout) or None.  Returns y's tensor."""
+    B, H, W, cout = int(B), int(H), int(W), int(cout)
+    if not isinstance(w_img, torch.Tensor) or not w_img.is_cuda or w_img.dtype != torch.float16 or not w_img.is_contiguous() or w_img.dim() != 5 \
+            or tuple(w_img.shape[3:]) != (64, 8) or int(w_img.shape[0]) not in (1, 9) or int(w_img.shape[2]) != 2 * ((cout + 31) // 32):
+        raise RuntimeError("fan_conv_f16: w_img must be a contiguous CUDA float16 image (1 | 9, Cin / 32, Cp / 16, 64, 8) for the channels stored")
+    ks, cin = (1 if int(w_img.shape[0]) == 1 else 3), 32 * int(w_img.shape[1])
+    if b is not None:
+        _req(b, "b")
+        if b.numel() != cout:
+            raise RuntimeError(f"fan_conv_f16: {b.numel()} biases for {cout} channels")
+    ia = ib = None
+    if affine is not None:
+        ia, ib = affine
+        _req(ia, "affine a"), _req(ib, "affine b")
+        if ia.numel() != cin or ib.numel() != cin:
+            raise RuntimeError(f"fan_conv_f16: an affine of {ia.numel()} / {ib.numel()} values for {cin} input channels")
+    n = B * H * W
+    ys, xs = _fan_win(y, "y", n, "float32" if out_f32 else "float16"), _fan_win(x, "x", n)
+    rw, r1, r2, u = _fan_win(raw, "raw", n), _fan_win(res1, "res1", n), _fan_win(res2, "res2", n), _fan_win(up, "up", B * (H // 2) * (W // 2))
+    flags = (FAN_RELU if relu else 0) | (FAN_OUT_F32 if out_f32 else 0)
+    check(lib.vsp_fan_conv_f16(ys[0], ys[1], ys[2], rw[0], rw[1], rw[2], xs[0], xs[1], xs[2], B, H, W, cin, cout, ks, flags, _ptr(w_img), _ptr(b),
+                               _ptr(ia), _ptr(ib), r1[0], r1[1], r1[2], r2[0], r2[1], r2[2], u[0], u[1], u[2], _stream()), "fan_conv_f16")
+    return y[0]
+
+
+def fan_decode(hm, pitch, box, B, n, K=68):
+    """Heatmaps -> landmarks (vsp_fan_decode_f32): hm a flat float32 buffer holding (B, n, n, pitch) with landmark k at channel k, box
+    (B, 3) float32 -> (lm (B, K, 2) float32 in image pixels, peak (B, K) float32, flag (B, K) int32: the map held a non-finite value)"""
+    _req(hm, "hm"), _req(box, "box")
+    B, n, K, pitch = int(B), int(n), int(K), int(pitch)
+    if hm.numel() < B * n * n * pitch or tuple(box.shape) != (B, 3):
+        raise RuntimeError(f"fan_decode: hm of {hm.numel()} floats, box {tuple(box.shape)} for ({B}, {n}, {n}, {pitch})")
+    lm = torch.empty((B, K, 2), device=hm.device, dtype=torch.float32)
+    peak = torch.empty((B, K), device=hm.device, dtype=torch.float32)
+    flag = torch.empty((B, K), device=hm.device, dtype=torch.int32)
+    check(lib.vsp_fan_decode_f32(_ptr(lm), _ptr(peak), _ptr(flag), _ptr(hm), pitch, _ptr(box), B, n, K, _stream()), "fan_decode")
+    return lm, peak, flag
+
+
 def _guard_public_ops():
     """every public operator of this module runs under `device_guarded` (helpers without tensor arguments pass straight through)"""
     import types

@@ -17,7 +17,7 @@ import os
 import torch
 
 WINDOWS = ("gauss11", "uniform7")
-COLUMNS = ("psnr", "ssim", "lpips", "id", "niqe")
+COLUMNS = ("psnr", "ssim", "lpips", "id", "niqe", "lmd", "nme")
 PEAK = 255.0
 
 
@@ -101,9 +101,15 @@ class Evaluator:
     `add` appends the batch's device features of the restored images -- and of the ground truth when the statistics are None --
     without a host synchronisation; `report()` makes one more copy, computes the Frechet distance on the host and keeps the features
     in `fid_features` (and `fid_gt_features`), in row order.  The rows do not change: FID is a property of the set.  With statistics,
-    `add(restored, None, names)` is legal like it is for NIQE."""
+    `add(restored, None, names)` is legal like it is for NIQE.
 
-    def __init__(self, window="gauss11", lpips=None, idloss=None, niqe=None, niqe_crop_border=0, fid=None):
+    `lmd` = a fan.FanLandmarks adds the columns `lmd` and `nme`: `add` runs restored and ground truth through the landmark
+    network in one batch and appends the per-image mean landmark distance in image pixels and that distance over the ground truth's
+    outer-eye-corner distance, both computed on the device; `lmd_box` = (x0, y0, s) is the square of every image the network sees
+    (default: the whole image).  An image of which a heatmap held a non-finite value gets None in both.  Like `lpips`, `lmd` needs the
+    ground truth."""
+
+    def __init__(self, window="gauss11", lpips=None, idloss=None, niqe=None, niqe_crop_border=0, fid=None, lmd=None, lmd_box=None):
         if window not in WINDOWS:
             raise ValueError(f"window must be one of {WINDOWS} (got {window!r})")
         self.window, self.lpips, self.idloss, self.niqe, self.niqe_crop_border = window, lpips, idloss, niqe, niqe_crop_border
@@ -113,7 +119,10 @@ class Evaluator:
         self.fid_dev, self.fid_gt_dev = [], []   # per batch (B, 2048) float32 on the device
         self.fid_features = self.fid_gt_features = None
         self.meta = []       # (index, lq, hq, samples per image; None without ground truth)
-        self.dev = {"sse": [], "ssim": [], "lpips": [], "id": []}
+        if lmd is None and lmd_box is not None:
+            raise ValueError("lmd_box only has a meaning with lmd")
+        self.lmd, self.lmd_box = lmd, lmd_box
+        self.dev = {"sse": [], "ssim": [], "lpips": [], "id": [], "lmd": [], "nme": []}
         self.niqe_feats = []  # per batch (B, nblk, 36) float64 on the device
 
     def __len__(self):
@@ -124,8 +133,8 @@ class Evaluator:
         if gt is None:
             if self.fid is not None and self.fid[1] is None:
                 raise RuntimeError("Evaluator.add without ground truth: FID without reference statistics is measured against the ground truth")
-            if (self.niqe is None and self.fid is None) or self.lpips is not None or self.idloss is not None:
-                raise RuntimeError("Evaluator.add without ground truth needs an Evaluator that scores NIQE only (niqe=params, no lpips / idloss)")
+            if (self.niqe is None and self.fid is None) or self.lpips is not None or self.idloss is not None or self.lmd is not None:
+                raise RuntimeError("Evaluator.add without ground truth needs an Evaluator that scores NIQE only (niqe=params, no lpips / idloss / lmd)")
             if self.dev["sse"]:
                 raise RuntimeError("Evaluator.add: this evaluator already holds batches with ground truth")
         if not isinstance(restored, torch.Tensor) or restored.dtype != torch.uint8 or (gt is not None and gt.dtype != torch.uint8):
@@ -161,6 +170,14 @@ class Evaluator:
                 if self.idloss is not None:
                     z = self.idloss.get_id(torch.cat([r, g], 0))
                     self.dev["id"].append((z[:B] * z[B:]).sum(1).to(torch.float64))
+        if self.lmd is not None:
+            from .fan import lmd_nme
+            # one batch of 2 B images: an image's landmarks do not depend on its place in it
+            lm, _, bad = self.lmd.landmarks(torch.cat([restored, gt], 0), self.lmd_box)
+            d, n = lmd_nme(lm[:B], lm[B:])
+            bad = bad[:B] | bad[B:]
+            self.dev["lmd"].append(torch.where(bad, torch.full_like(d, float("nan")), d))
+            self.dev["nme"].append(torch.where(bad, torch.full_like(n, float("nan")), n))
         count = restored.shape[1] * restored.shape[2] * restored.shape[3]
         self.meta.extend((i, n[0], n[1], count) for i, n in zip(indices, names))
 
@@ -191,6 +208,9 @@ class Evaluator:
                     row[col] = host[col][k]
             if scores is not None:
                 row["niqe"] = scores[k]
+            for col in ("lmd", "nme"):     # a non-finite heatmap (or a ground truth whose eye corners coincide) has no figure
+                if col in host:
+                    row[col] = host[col][k] if math.isfinite(host[col][k]) else None
             rows.append(row)
         report = summarize(rows, dataset, self.window)
         if self.fid is not None:

@@ -2,7 +2,7 @@
 
     python -m vspbfr_amd.restoration_metrics <the flags of vspbfr_amd.restoration_test> \\
         [--ingest host|device [--decode host|device]] [--encode host|device] --metrics [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH]
-        [--niqe_params NPZ] [--fid_weights W [--fid_stats S]]
+        [--niqe_params NPZ] [--fid_weights W [--fid_stats S]] [--lmd_weights W [--lmd_box X0,Y0,SIDE]]
 
 `vspbfr_amd/restoration_test.py` stays the line-by-line counterpart of the reference's script and is not edited: its file name
 puts it under this repository's rule that a feature leaves every existing `*_test.py` / `test_*.py` file as it is.  This module
@@ -16,7 +16,8 @@ summary line printed.  `--metrics` is off by default: without it the output dire
 `vspbfr_amd.niqe_fit`) is given: then every report gains the no-reference `niqe` column of the restored image, and a dataset without
 ground truth gets a report with that column alone.  `--fid_weights W` adds the report's `fid` entry (against the ground truth,
 or against `--fid_stats S`, which also lets a dataset without ground truth be scored) and writes `fid_features_<rank>.npy` beside the
-report.  Multi-GPU as restoration_test; `metrics.merge_reports`
+report.  `--lmd_weights W` (a 2D-FAN state dict) adds the `lmd` and `nme` columns of every dataset, which must all have
+ground truth; `--lmd_box` names the square of every image the landmark network sees.  Multi-GPU as restoration_test; `metrics.merge_reports`
 joins the per-rank files."""
 import argparse
 import os
@@ -67,6 +68,8 @@ def tester_restore_ddpm(args, pipe, lq_root, hq_root, eval_dict, data_name, devi
         # a dataset without ground truth is scored by NIQE alone (main() has refused it already when no model was given)
         fid = getattr(args, "fid", None)
         kw = {} if fid is None else {"fid": fid}
+        if getattr(args, "lmd", None) is not None:
+            kw.update(lmd=args.lmd, lmd_box=args.lmd_box_value)
         evaluator = Evaluator(args.ssim_window, *args.scorers, niqe=niqe_params, **kw) if data.hq is not None else Evaluator(
             args.ssim_window, niqe=niqe_params, **kw)
     print("testing!!! len:%d (rank %d handles %d..%d)" % (len(data), rank, lo, hi))
@@ -135,7 +138,11 @@ def main(argv=None):
     ap.add_argument("--fid_stats", type=str, default=None,
                     help="extension: .npz or torch file with mu / sigma: FID against these statistics instead of the ground truth; lets a "
                          "dataset without ground truth be scored")
+    from .fan import add_lmd_arguments, check_lmd_arguments
+    add_lmd_arguments(ap)
     args = ap.parse_args(argv)
+    args.lmd_box_value = check_lmd_arguments(ap, args, args.metrics, all(
+        d["hq"] not in ("None", "") for d in get_store_data(args.lq_data_list, args.hq_data_list, args.data_name_list)))
     if not args.metrics and (args.fid_weights or args.fid_stats):
         ap.error("--fid_weights / --fid_stats only have a meaning with --metrics")
     if args.fid_stats and not args.fid_weights:
@@ -193,6 +200,9 @@ def main(argv=None):
         if args.fid_weights:
             from . import fid as fid_mod
             args.fid = (fid_mod.FidInception(fid_mod.load(args.fid_weights), device), args.fid_ref, args.fid_stats)
+        if args.lmd_weights:
+            from .fan import FanLandmarks
+            args.lmd = FanLandmarks(args.lmd_weights, device)
     for k, d in enumerate(store):
         diffusion = load_ddpm(args.ddpm_ckpt, device=device, timesteps=args.timesteps)
         pipe = RestorationPipeline(g_ema, psp, diffusion, mixing=args.mixing, with_sample=not args.no_sample)

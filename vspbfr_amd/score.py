@@ -3,7 +3,7 @@
 
     python -m vspbfr_amd.score --restored eval_dir/.../demo --gt eval_dir/.../demo [--pattern _restore.png/_gt.png]
         [--ssim_window gauss11|uniform7] [--lpips_weights LIN[,VGG]] [--id_weights PATH] [--niqe_params NPZ]
-        [--fid_weights W [--fid_stats S]] [--batch 8] [--out metrics.json]
+        [--fid_weights W [--fid_stats S]] [--lmd_weights W [--lmd_box X0,Y0,SIDE]] [--batch 8] [--out metrics.json]
 
 `--niqe_params` (a pristine model, `vspbfr_amd.niqe_fit` or a published one) adds the no-reference `niqe` column and makes --gt
 optional: without --gt every file of --restored that carries the restored suffix (all files when none does) is scored alone.
@@ -11,6 +11,10 @@ optional: without --gt every file of --restored that carries the restored suffix
 `--fid_weights` (an FID Inception state dict, `vspbfr_amd.fid`) adds the report's top-level `fid` entry: against the ground truth's
 features, or against `--fid_stats` (mu / sigma of a reference set), which makes --gt optional too.  With --out the features go to
 `<out stem>_fid_features.npy` (and `..._gt.npy`) beside the report, so that `metrics.merge_reports` can recompute the distance.
+
+`--lmd_weights` (a 2D-FAN state dict, `vspbfr_amd.fan`) adds the `lmd` and `nme` columns: the mean distance between the 68 landmarks
+found on the restored image and on its ground truth, in image pixels and over the ground truth's outer-eye-corner distance; `--lmd_box`
+names the square of every image the landmark network sees (default: the whole image).  It needs --gt.
 
 Pairing: a file `<stem><restored suffix>` of --restored goes with `<stem><gt suffix>` of --gt (the CLI's own naming,
 `{index}_{rank}_{name}_restore.png` / `..._gt.png`); when no file of --restored carries the suffix, the two folders are
@@ -60,14 +64,16 @@ def restored_files(restored_dir, pattern="_restore.png/_gt.png"):
     return [(p, None) for p in (tagged or files)]
 
 
-def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda", niqe=None, fid=None, evaluator=None):
+def score_pairs(pairs, window="gauss11", lpips=None, idloss=None, batch=8, dataset=None, device="cuda", niqe=None, fid=None, evaluator=None,
+                lmd=None, lmd_box=None):
     """The report of a list of (restored, gt) files; images of one size are batched, an odd one goes alone.  gt = None in every
     pair (with `niqe` params or `fid` statistics): the no-reference report.  `fid`: metrics.Evaluator's argument; `evaluator`: a list
-    that receives the Evaluator (its FID features go to disk beside the report)."""
+    that receives the Evaluator (its FID features go to disk beside the report); `lmd` / `lmd_box`: metrics.Evaluator's arguments."""
     import torch
 
     from .metrics import Evaluator
-    ev = Evaluator(window, lpips, idloss, niqe) if fid is None else Evaluator(window, lpips, idloss, niqe, fid=fid)
+    kw = {} if lmd is None else {"lmd": lmd, "lmd_box": lmd_box}
+    ev = Evaluator(window, lpips, idloss, niqe, **kw) if fid is None else Evaluator(window, lpips, idloss, niqe, fid=fid, **kw)
     if evaluator is not None:
         evaluator.append(ev)
     pend, shape = [], None
@@ -102,6 +108,8 @@ def main(argv=None):
     ap.add_argument("--niqe_params", default=None, help=".npz with mu_pris_param / cov_pris_param; adds the niqe column")
     ap.add_argument("--fid_weights", default=None, help="FID Inception state dict (pt_inception layout); adds the report's fid entry")
     ap.add_argument("--fid_stats", default=None, help=".npz or torch file with mu / sigma: FID against these statistics instead of --gt")
+    from .fan import add_lmd_arguments, check_lmd_arguments
+    add_lmd_arguments(ap)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--dataset", default=None, help="name written into the report")
     ap.add_argument("--out", default=None, help="write the JSON report here (default: print it)")
@@ -116,6 +124,7 @@ def main(argv=None):
         ap.error("--gt is required unless --niqe_params asks for the no-reference score")
     if args.gt is None and (args.lpips_weights or args.id_weights):
         ap.error("--lpips_weights / --id_weights compare against ground truth: they need --gt")
+    lmd_box = check_lmd_arguments(ap, args, True, args.gt is not None)
     niqe_params = fid_stats = None
     try:
         if args.fid_stats:
@@ -133,7 +142,14 @@ def main(argv=None):
     if args.fid_weights:
         from . import fid as fid_mod
         fid = (fid_mod.FidInception(fid_mod.load(args.fid_weights), "cuda"), fid_stats, args.fid_stats)
-    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset, niqe=niqe_params, fid=fid, evaluator=held)
+    kw = {}
+    if args.lmd_weights:
+        from .fan import FanLandmarks
+        try:
+            kw = {"lmd": FanLandmarks(args.lmd_weights, "cuda"), "lmd_box": lmd_box}
+        except ValueError as e:
+            ap.error(str(e))
+    report = score_pairs(pairs, args.ssim_window, lp, idl, args.batch, args.dataset, niqe=niqe_params, fid=fid, evaluator=held, **kw)
     if args.out and fid is not None:
         from .metrics import write_report_with_features
         write_report_with_features(held[0], report, args.out)
