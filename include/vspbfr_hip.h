@@ -240,6 +240,19 @@ size_t vsp_winograd4f_weight_floats(int cin, int cout);
 int vsp_winograd4f_weight_f32(float* U, const float* wp, int cin, int cout, vsp_stream_t stream);
 int vsp_conv2d_winograd4f_f32(const vsp_conv_params* params, vsp_stream_t stream);
 
+/* The stride-2 transposed 3x3 convolution (`transposed` = 1: the launch of vsp_conv2d_f32's transposed mode, same operands, output extents,
+ * y_coff and epilogue chain) as a fused Winograd F(2x2,2x2) phase kernel (conv_tconv_wino.hip): a tile of 2 x 2 positions = 4 x 4 outputs takes
+ * 9 + 6 + 6 + 4 = 25 products per (ci, co) where the direct form takes 36; every transform constant is 0 or +-1.  Serves one group, fp32,
+ * Cin % 4 == 0, the style scale `in_scale` but no `in_shift`, 16-byte aligned output planes.  VSP_ENOTSUP for a launch it does not serve:
+ * nothing is written and the caller falls back to vsp_conv2d_f32.
+ * `w` = vsp_tconvw_weight_f32's output: the 16 distinct transformed weights the 25 products read (g_0 = tap 2, g_1 = tap 2 + tap 0, g_2 = tap 0
+ * on a 2-tap axis; fp64 sums of the packed weights times `scale`, rounded once) as U[3 i + j] = gy_i gx_j W (phase (0,0)), U[9 + i] = gy_i W[., 1],
+ * U[12 + j] = gx_j W[1, .], U[15] = W[1, 1], in the order [co / 16][ci / 4][quad 4][lane 64][4]: lane = 16 (ci % 4) + (co % 16), element e of
+ * quad q = U[4 q + e]; channels past Cin / Cout are zeros. */
+size_t vsp_tconvw_weight_floats(int cin, int cout);
+int vsp_tconvw_weight_f32(float* U, const float* wp, int cin, int cout, float scale, vsp_stream_t stream);
+int vsp_conv_transpose2d_s2_wino_f32(const vsp_conv_params* params, vsp_stream_t stream);
+
 size_t vsp_conv2d_winograd4_work_floats(const vsp_conv_params* p);
 size_t vsp_winograd4_weight_floats(int cin, int cout);
 int vsp_winograd4_weight_f32(float* U, const float* wp, int cin, int cout, vsp_stream_t stream);

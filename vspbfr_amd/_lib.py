@@ -208,6 +208,8 @@ SIGNATURES = {
     "vsp_conv2d_winograd4_f32": [_p, _p, C.c_size_t, _p],
     "vsp_winograd4f_weight_f32": [_p, _p, _i, _i, _p],
     "vsp_conv2d_winograd4f_f32": [_p, _p],
+    "vsp_tconvw_weight_f32": [_p, _p, _i, _i, _f, _p],
+    "vsp_conv_transpose2d_s2_wino_f32": [_p, _p],
     "vsp_modulate_weight_bf16": [_p, _p, _p, _i, _i64, _i, _i, _i, _p],
     "vsp_conv2d_winograd_chunk": [],
     "vsp_conv2d_winograd_mbw": [_i],
@@ -268,6 +270,7 @@ SIGNATURES = {
 _CHARP = {"vsp_last_error": [], "vsp_conv2d_config_name": [_i]}
 _SIZET = {"vsp_tacc_chain_work_floats": [_i], "vsp_conv2d_wgrad_work_floats": [C.POINTER(ConvWgradParams)],
           "vsp_winograd_weight_floats": [_i, _i, _i], "vsp_winograd4_weight_floats": [_i, _i], "vsp_winograd4f_weight_floats": [_i, _i],
+          "vsp_tconvw_weight_floats": [_i, _i],
           "vsp_conv2d_winograd4_work_floats": [_p], "vsp_modulate_weight_bf16_bytes": [_i, _i, _i],
           "vsp_pair_stats_work_bytes": [_i, _i, _i, _i, _i], "vsp_lanczos_work_bytes": [_i, _i],
           "vsp_png_segment_bound": [_i, _i, _i], "vsp_png_bound": [_i, _i, _i],

@@ -477,6 +477,37 @@ extern "C" int vsp_conv2d_winograd4f_f32(const vsp_conv_params* pp, vsp_stream_t
   return vsp::check_launch(who);
 }
 
+extern "C" size_t vsp_tconvw_weight_floats(int cin, int cout) { return vspconv::tconvw_weight_floats(cin, cout); }
+
+extern "C" int vsp_tconvw_weight_f32(float* U, const float* wp, int cin, int cout, float scale, vsp_stream_t stream) {
+  VSP_REQUIRE(U && wp && cin >= 1 && cout >= 1, "tconvw_weight: bad arguments");
+  VSP_REQUIRE(vsp::aligned16(U), "tconvw_weight: the weight image must be 16-byte aligned");
+  if (int rc = vspconv::tconvw_weight_launch(U, wp, cin, cout, scale, vsp::as_stream(stream))) return rc;
+  return vsp::check_launch("tconvw_weight");
+}
+
+extern "C" int vsp_conv_transpose2d_s2_wino_f32(const vsp_conv_params* pp, vsp_stream_t stream) {
+  const char* who = "conv_transpose2d_s2_wino";
+  VSP_REQUIRE(pp != nullptr, "conv_transpose2d_s2_wino: null params");
+  vsp_conv_params pcopy = *pp;
+  // what the kernel does not serve is refused before anything is launched or written: the caller falls back to vsp_conv2d_f32
+  if (!pcopy.transposed || pcopy.KH != 3 || pcopy.KW != 3 || pcopy.G != 1 || pcopy.x_group_stride != 0 || pcopy.dil_by_input_quarter)
+    return vsp::fail(VSP_ENOTSUP, "conv_transpose2d_s2_wino: serves the stride-2 transposed 3x3 conv of one group");
+  if (pcopy.io_bf16 || pcopy.in_shift != nullptr || pcopy.Cin % 4 != 0)
+    return vsp::fail(VSP_ENOTSUP, "conv_transpose2d_s2_wino: fp32, no affine input shift, Cin %% 4 == 0");
+  if (int rc = normalise_transposed(who, pcopy, false)) return rc;
+  const vsp_conv_params& p = pcopy;
+  if (int rc = require_input_under_2gib(who, p)) return rc;
+  ConvK q{};
+  bool empty = false;
+  if (int rc = conv_front(p, q, &empty)) return rc;
+  if (empty) return VSP_OK;
+  if (!vspconv::tconvw_eligible(q))
+    return vsp::fail(VSP_ENOTSUP, "conv_transpose2d_s2_wino: needs 16-byte aligned weight image and output planes, < 2 GiB per image");
+  if (int rc = vspconv::tconvw_launch(q, vsp::as_stream(stream))) return rc;
+  return vsp::check_launch(who);
+}
+
 enum Bf16Kernel { kBf16General, kBf16Split, kBf16RowVector, kBf16DilationGroups };   // conv_bf16.hip (plain, hi + lo operands), conv_bf16_rv.hip, conv_bf16_dg.hip
 static int conv2d_bf16_impl(const vsp_conv_params* pp, vsp_stream_t stream, Bf16Kernel kern);
 extern "C" int vsp_conv2d_bf16(const vsp_conv_params* pp, vsp_stream_t stream) { return conv2d_bf16_impl(pp, stream, kBf16General); }

@@ -652,6 +652,11 @@ bool wino4f_eligible(const ConvK& q);
 size_t wino4f_weight_floats(int cin, int cout);
 int wino4f_weight_launch(float* U, const float* wp, int cin, int cout, hipStream_t stream);
 int wino4f_launch(ConvK q, hipStream_t stream);
+// conv_tconv_wino.hip: the stride-2 transposed 3x3 conv as a fused Winograd F(2x2,2x2) phase kernel (25 of the 36 products)
+bool tconvw_eligible(const ConvK& q);
+size_t tconvw_weight_floats(int cin, int cout);
+int tconvw_weight_launch(float* U, const float* wp, int cin, int cout, float scale, hipStream_t stream);
+int tconvw_launch(const ConvK& q, hipStream_t stream);
 int wino_chunk();           // input channels per chunk the transformed-weight layout is built for
 int wino_mbw(int cout_g);   // 16-channel blocks per workgroup (fragment layout) for a layer with cout_g channels per group
 

@@ -44,7 +44,8 @@ class ConvProfiler:
     def executed_flops(self):
         """FLOPs the matrix pipe actually EXECUTED: a Winograd F(2x2,3x3) launch runs 16 multiplies per 2x2 output tile where the
         direct form (the algorithmic count of `summary`) has 36; every other kernel executes its algorithmic count."""
-        f = {"wino": 16.0 / 36.0, "wino4": 36.0 / 144.0, "wino4f": 36.0 / 144.0}   # F(4x4,3x3): 36 multiplies per 4x4 tile against 144
+        f = {"wino": 16.0 / 36.0, "wino4": 36.0 / 144.0, "wino4f": 36.0 / 144.0,   # F(4x4,3x3): 36 multiplies per 4x4 tile against 144
+             "tconvw": 25.0 / 36.0}   # transposed F(2x2,2x2) phases: 25 multiplies per 2x2 positions against 36
         return sum(r[0] * (f.get(r[3][7], 1.0) if len(r[3]) > 7 else 1.0) for r in self.records)
 
     def by_kind(self):
@@ -573,6 +574,60 @@ def winograd4f_weight(wp):
     return U
 
 
+def _load_tconvw_allow():
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tconv_wino_allow.json")
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return {k: True for k in json.load(f)}
+
+
+# the up-convs on the fused Winograd phase kernel: True = the shapes of TCONVW_ALLOW (tconv_wino_allow.json: shape keys where it measured
+# >= 5 % faster than the direct launch in the same process, tools/bench_tconv_wino.py; looked up by the exact key -- another batch size
+# was not measured and keeps the direct kernel and its bits), "all" = every launch it serves (tests, A/B runs), False = never
+TCONV_WINO = True
+TCONVW_ALLOW = _load_tconvw_allow()
+
+
+def tconvw_eligible(pc, transposed=True, in_shift=False, io_bf16=False):
+    """What vsp_conv_transpose2d_s2_wino_f32 serves (the entry re-checks, alignment included, and returns VSP_ENOTSUP): the stride-2
+    transposed 3x3 conv of one group, fp32, no affine shift, Cin a multiple of 4."""
+    return bool(transposed and pc.kh == 3 and pc.kw == 3 and pc.G == 1 and pc.x_group_stride == 0 and not pc.dil_by_input_quarter
+                and not in_shift and not io_bf16 and pc.cin % 4 == 0)
+
+
+def tconvw_weight_host(wp, scale=1.0):
+    """Host restatement of vsp_tconvw_weight_f32 on a packed weight (1, 9, Cin, Cout) -> (16, Cin, Cout): the 16 distinct transformed weights of
+    the 25 products (g_0 = tap 2, g_1 = tap 2 + tap 0, g_2 = tap 0 on a 2-tap axis), fp64 sums rounded once."""
+    w = wp[0].double().reshape(3, 3, wp.shape[2], wp.shape[3]) * torch.tensor(scale, dtype=torch.float32).double()   # (the entry takes a float)
+    g = torch.tensor([[0., 0., 1.], [1., 0., 1.], [1., 0., 0.]], dtype=torch.float64)
+    u00 = torch.einsum("ik,jl,klco->ijco", g, g, w).reshape(9, *w.shape[2:])
+    u01 = torch.einsum("ik,kco->ico", g, w[:, 1])
+    u10 = torch.einsum("jl,lco->jco", g, w[1])
+    return torch.cat([u00, u01, u10, w[1, 1][None]], 0).float()
+
+
+def tconvw_weight(wp, scale=1.0):
+    """packed weights (1, 9, Cin, Cout) -> the U image of vsp_conv_transpose2d_s2_wino_f32 ([co / 16][ci / 4][quad 4][lane 64][4],
+    include/vspbfr_hip.h)."""
+    wp = _req(wp, "packed weight")
+    ng, taps, cin, cout = wp.shape
+    if ng != 1 or taps != 9:
+        raise RuntimeError("tconvw_weight: one group of 3x3 taps")
+    U = torch.empty(lib.vsp_tconvw_weight_floats(cin, cout), device=wp.device, dtype=torch.float32)
+    check(lib.vsp_tconvw_weight_f32(_ptr(U), _ptr(wp), cin, cout, float(scale), _stream()), "tconvw_weight")
+    return U
+
+
+def tconvw_unpack(U, cin, cout):
+    """The U image back as (16, Cin, Cout) (tests: the inverse of the fragment order)."""
+    ncb, nks = (cout + 15) // 16, (cin + 3) // 4
+    u = U.view(ncb, nks, 4, 4, 16, 4).permute(2, 5, 1, 3, 0, 4).reshape(16, nks * 4, ncb * 16)   # [q][e][ks][kq][cb][lr]
+    return u[:, :cin, :cout]
+
+
 def winograd4f_eligible(pc, H, W, OH, OW, transposed=False, out_stride=(1, 1), out_offset=(0, 0), in_shift=None):
     """fused F(4x4,3x3): one group or up to four dilation groups over one shared input, 3x3 / stride 1 / padding = dilation in (1, 2, 4, 8)
     -- dilated groups run on their polyphase sub-images: whole 4x4 tiles in each (H, W multiples of 4 x dilation) --, no affine shift, Cin a
@@ -688,6 +743,24 @@ def _launch_f32(p, pc, keep, named, in_scale):
     return "tconv" if p.transposed else "direct"
 
 
+def _launch_tconv(p, pc, keep, named, in_scale):
+    """The up-convs: the fused Winograd phase kernel (vsp_conv_transpose2d_s2_wino_f32, 25 of the 36 products) where TCONV_WINO asks for it --
+    True: on the shapes of TCONVW_ALLOW, "all": on every launch it serves -- and the caller named no tile of the direct kernel; else, and on
+    VSP_ENOTSUP, the transposed mode of vsp_conv2d_f32."""
+    want = TCONV_WINO and p.tile_hint <= 0 and tconvw_eligible(pc, p.transposed, p.in_shift is not None, p.io_bf16) and (
+        TCONV_WINO == "all" or (conv_key(p.B, pc.cin, p.H, p.W, pc, p.OH, p.OW) + ",t") in TCONVW_ALLOW)   # (the measured key itself: no batch-8 stand-in)
+    if want:
+        hint = p.tile_hint
+        _set_weight(p, keep, pc.form("tconvw"))
+        p.tile_hint = 0
+        rc = lib.vsp_conv_transpose2d_s2_wino_f32(C.byref(p), _stream())
+        if rc != -3:
+            check(rc, "conv_transpose2d_s2_wino")
+            return "tconvw"
+        p.w, p.tile_hint = pc.w.data_ptr(), hint   # VSP_ENOTSUP (alignment of an operand plane): nothing was written
+    return _launch_f32(p, pc, keep, named, in_scale)
+
+
 def _launch_wino(p, pc, keep, named, in_scale):
     _set_weight(p, keep, pc.form("wino"))
     check(lib.vsp_conv2d_winograd_f32(C.byref(p), _stream()), "conv2d_winograd")
@@ -769,7 +842,7 @@ def _launch_bf16dg(p, pc, keep, named, in_scale):
     return "bf16dg"
 
 
-_LAUNCH = {"direct": _launch_f32, "tconv": _launch_f32, "wino": _launch_wino, "wino4": _launch_wino4, "wino4f": _launch_wino4f,
+_LAUNCH = {"direct": _launch_f32, "tconv": _launch_tconv, "wino": _launch_wino, "wino4": _launch_wino4, "wino4f": _launch_wino4f,
            "bf16": _launch_bf16, "bf16x3": _launch_bf16x3, "bf16rv": _launch_bf16rv, "bf16dg": _launch_bf16dg}
 
 
@@ -2679,5 +2752,5 @@ def _guard_public_ops():
 
 _guard_public_ops()
 # PackedConv.form: kernel family -> its weight layout (the device-guarded builders)
-WEIGHT_FORMS = {"wino": winograd_weight, "wino4": winograd4_weight, "wino4f": winograd4f_weight, "bf16": bf16_weight, "bf16x3": bf16x3_weight,
+WEIGHT_FORMS = {"wino": winograd_weight, "wino4": winograd4_weight, "wino4f": winograd4f_weight, "tconvw": tconvw_weight, "bf16": bf16_weight, "bf16x3": bf16x3_weight,
                 "bf16rv": bf16rv_weight, "bf16dg": bf16dg_weight}
