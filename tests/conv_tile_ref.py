@@ -86,6 +86,7 @@ class Shape:
     transposed: bool = False
     t_margin: tuple = (0, 0)      # transposed: rows / columns of the output plane beyond (2H+1) x (2W+1)
     w_off: int = 0                # bytes between the weight's first element and a 16-byte boundary
+    quarter: bool = False         # dil_by_input_quarter (tests/conv_pipe_ref.py): G = 4 blocks of output channels, dilation by input quarter
 
 
 @dataclass(frozen=True)
@@ -194,6 +195,8 @@ def operands(case):
             o.update(noise=True, res=2, res_coff=2, res_pad=3)
     elif ch == "demod":     # (tests/conv_bf16_ref.py: what a modulated layer without activation hands over -- style, demodulation, scale and bias)
         o.update(in_scale="sample", out_scale=True, ch_scale=True, ch_bias=True)
+    elif ch == "modonly":   # (tests/conv_pipe_ref.py: what an up-conv of the path hands over -- style and demodulation, nothing else)
+        o.update(in_scale="sample", out_scale=True)
     elif ch == "bn":
         o.update(in_scale="channel", in_shift=not tg, ch_scale=True, ch_bias=True, act2=2, bias2=True)
     elif ch in SLOPES:
@@ -281,10 +284,12 @@ def _accumulate(case, d, dtype, wrong):
     """acc[b, co, oy, ox] of the header, tap by tap from the packed weight"""
     g = geom(case)
     B, Cin, H, W, KH, KW = case.B, case.Cin, case.H, case.W, case.KH, case.KW
-    x = d["x"].to(dtype)
+    x = xraw = d["x"].to(dtype)
+    scb = None
     if "in_scale" in d:
         sc = d["in_scale"].to(dtype)
-        x = x * (sc[:, :, None, None] if sc.dim() == 2 else sc[None, :, None, None])
+        scb = sc[:, :, None, None] if sc.dim() == 2 else sc[None, :, None, None]
+        x = x * scb
     sh = d["in_shift"].to(dtype)[None, :, None, None] if "in_shift" in d else None
     wp = d["wp"].to(dtype)
     if case.transposed:
@@ -308,6 +313,28 @@ def _accumulate(case, d, dtype, wrong):
         return acc[:, :, :2 * H + 1, :2 * W + 1]
     acc = torch.zeros(B, g.Cout, g.OH, g.OW, dtype=dtype)
     sy, sx = (case.sx, case.sy) if wrong == "stride_swap" else (case.sy, case.sx)
+    if case.quarter:
+        # dil_by_input_quarter: y = sum_q conv(x[quarter q], W[:, quarter q], dilation = padding = d_q) over all G * cout_g output channels;
+        # the weight image is Wp[block][tap][ci][co] with ci over the whole input (tests/test_hip_ops.py, vspbfr_amd/training.py)
+        c4 = Cin // 4
+        for q in range(4):
+            dl = case.dil[0] if (wrong == "group_dil0" or (wrong == "quarter_dil0" and q == 3)) else case.dil[q]
+            qw = {1: 2, 2: 1}.get(q, q) if wrong == "quarter_w_swap" else q      # quarters 1 and 2 read each other's weight rows
+            xs = x[:, q * c4:(q + 1) * c4]
+            for ky in range(3):
+                iy = torch.arange(g.OH) + (ky - 1) * dl
+                my = (iy >= 0) & (iy < H)
+                rows = xs[:, :, iy.clamp(0, H - 1)]
+                for kx in range(3):
+                    ix = torch.arange(g.OW) + (kx - 1) * dl
+                    m = (my[:, None] & ((ix >= 0) & (ix < W))[None, :]).to(dtype)
+                    v = rows[:, :, :, ix.clamp(0, W - 1)] * m
+                    if sh is not None:
+                        v = v + sh[:, q * c4:(q + 1) * c4] * (1.0 if wrong == "shift_on_pad" else m)
+                    tap = kx * 3 + ky if wrong == "taps_transposed" else ky * 3 + kx
+                    for blk in range(4):
+                        acc[:, blk * case.cout_g:(blk + 1) * case.cout_g] += torch.einsum("bchw,co->bohw", v, wp[blk, tap, qw * c4:(qw + 1) * c4])
+        return acc
     for grp in range(case.G):
         gi = 0 if (case.G > 4 or wrong == "group_dil0") else grp      # more than four groups share the geometry of group 0
         dl, py, px = case.dil[gi], case.pad_y[gi], case.pad_x[gi]
@@ -315,7 +342,10 @@ def _accumulate(case, d, dtype, wrong):
             py, px = px, py
         c0 = 0 if wrong == "group_slice0" else grp * case.x_gs
         xs = x[:, c0:c0 + Cin]
-        out = acc[:, grp * case.cout_g:(grp + 1) * case.cout_g]
+        if wrong == "group_scale0" and scb is not None:      # the group's own input under the scale of group 0
+            xs = xraw[:, c0:c0 + Cin] * scb[:, :Cin]
+        og = (grp + 1) % case.G if wrong == "group_out_swap" else grp      # written to the channels of the next group
+        out = acc[:, og * case.cout_g:(og + 1) * case.cout_g]
         for ky in range(KH):
             iy = torch.arange(g.OH) * sy + ky * dl - py
             my = (iy >= 0) & (iy < H)
@@ -393,6 +423,8 @@ def reference(case, d, dtype, wrong=None, acc=None):
         win = y[:, g.y_coff:g.y_coff + g.Cout, :2 * case.H + 1, :2 * case.W + 1]
         if wrong == "last_col_dropped":
             win[..., :2 * case.W] = v[..., :2 * case.W]
+        elif wrong == "last_row_dropped":
+            win[..., :2 * case.H, :] = v[..., :2 * case.H, :]
         else:
             win.copy_(v)
         return y

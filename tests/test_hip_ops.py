@@ -1814,7 +1814,12 @@ def test_conv_smallmap_kernel(H, case):
 def test_conv_pipelined_kernels(H, case):
     """Every configuration of the double-buffered pipeline kernels (conv_pipe.hip, names "...p3...") that accepts the launch: the
     plain convolution against F.conv2d / F.conv_transpose2d in float64, then every prologue / epilogue operand of the contract
-    against the tiled kernel (conv_igemm_kernel) on the same launch parameters."""
+    against the tiled kernel (conv_igemm_kernel) on the same launch parameters.
+
+    A smoke test of the family through conv2d_packed: an instance that refuses a shape is skipped here, and y is allocated exactly.  Which of the
+    33 instances serves which case, every refusal by its rule, the sentinel around the written region, separate strides and pads, channel
+    windows, workgroup order 2 and every nchunk class of the `fd` interval are held by tests/test_conv_pipe_forms_gpu.py (each case on every
+    instance by name against float64 under conv_tile_ref.bound), with tests/test_conv_pipe_ref.py proving the reach of its table."""
     from vspbfr_amd._lib import lib
     c = case
     g_ = torch.Generator().manual_seed(53)
@@ -1904,7 +1909,11 @@ def test_conv_pipelined_kernels(H, case):
 @pytest.mark.parametrize("cin,cout,hw", [(64, 64, (40, 56)), (128, 32, (33, 20)), (64, 128, (16, 16))])
 def test_conv_dilation_by_input_quarter(H, cin, cout, hw):
     """vsp_conv_params.dil_by_input_quarter (conv_pipe.hip MODE 3): y = sum_q conv(x[q-th quarter], W_q, dilation = padding = d_q) as
-    ONE convolution -- the data gradient of the four dilated SMART branches -- with the per-sample input / output scales and a bias."""
+    ONE convolution -- the data gradient of the four dilated SMART branches -- with the per-sample input / output scales and a bias.
+
+    tile_hint = 0 takes the first `a` instance of the table that fits, which is 4x2x1x8x4k1p3o2r8a for all three shapes; the four `a` instances
+    by name, the (Cin / 4) % CK refusal, 12 channels per block, dilations other than 1, 2, 4, 8 and the whole epilogue chain are in
+    tests/test_conv_pipe_forms_gpu.py (shapes a16 ... a128, a64d of tests/conv_pipe_ref.py)."""
     g_ = torch.Generator().manual_seed(31)
     B, rates, c = 2, (1, 2, 4, 8), cin // 4
     x = torch.randn(B, cin, *hw, generator=g_)
@@ -1949,7 +1958,8 @@ def test_conv_pipelined_refuses_what_it_does_not_serve(H):
 
 def test_conv_smallmap_random_shapes(H):
     """Thirty seeded random small-map problems (ragged channel counts, odd maps, both strides, dilation, 1x1 / 3x3 / 5x5 kernels,
-    batch 1..9): the small-map kernel against F.conv2d in float64, with the per-sample input scale folded in."""
+    batch 1..9): the small-map kernel against F.conv2d in float64, with the per-sample input scale folded in.  (G = 1 and in_scale only; which
+    of the five instantiations a launch takes, groups, in_shift, placement and the epilogue chain: tests/test_conv_pipe_forms_gpu.py.)"""
     rng = np.random.default_rng(77)
     sm = H.CONFIG_IDS["smallmap"]
     for it in range(30):
